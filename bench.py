@@ -14,7 +14,14 @@ torch.distributed.run (WORLD_SIZE set), it is one of the ranks; WORLD_SIZE != --
 `--dry-launch` runs the same launcher / rendezvous / barrier / max-over-ranks timing with the gloo backend and NO GPU work
 (tests/test_host_logic.py: the launcher is exercised on CPU).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly --steps steps, writes the outputs of the last
+one (--dump-outputs) and prints the headline: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (the
+milliseconds of one timed step) and the configuration.  `--dump-outputs DIR` writes what the timed path computed in its
+last timed step as float32 .npy files (dump_outputs); the inputs, weights and noise are seeded, so two runs with the same
+arguments see the same inputs and two builds can be compared output for output.
+
+`--full` adds the side measurements below (each with its own runs after the timed region); `--no-cpu-baseline`,
+`--no-roofline` and `--no-other-configs` drop single ones of them again:
   roofline     dominant kernel family = the contraction kernel gemm_f32_kernel (every Linear, LSTM input projection,
                weight gradient and k5 conv), AND its single dominant instantiation (template arguments named).
                achieved = algorithmic FLOPs of the launches / their summed duration, measured HERE with HIP events
@@ -36,15 +43,17 @@ Rank 0 prints ONE JSON line.  Extra objects:
   cpu_baseline the CPU oracle (oracle/dvae_ref.py, the verified restatement of the reference's PyTorch-CPU step)
                timed on this box's host cores on the same workload, rank 0, N=1 only: once with 64 threads and once
                with all physical cores; `value` is the FASTER of the two, both samples listed.
-  N > 1        the EAGER data-parallel step, timed once per exchange variant — bucketed all-reduce or reduce-scatter +
-               sharded Adam + all-gather, collectives issued from the backward hooks or after backward — each over exactly
-               --steps steps (ddp_variants_ms_per_step); the headline is the fastest (no multi-GPU box has been available to
-               choose in advance).  The step with the collectives captured inside the hipGraph is attempted only with
-               DVAE_BENCH_DDP_GRAPH=1.  Diagnostics: rccl_ranks, visible devices, per-rank ms, buckets,
-               allreduce_exposed_ms (step minus the same step with the reducer detached).  The line carries the SAME objects
-               as the N = 1 line: roofline / roofline_lstm (rank 0 alone, reducer detached, after the timed variants),
-               cpu_baseline (after the process group is gone) and scaling_vs_n1 (value / the single-rank graph-replayed step
-               timed in the same processes, all ranks at once; DVAE_BENCH_N1_MS supplies a number measured elsewhere).  A
+  N > 1        the EAGER data-parallel step of the default exchange is the headline (ddp_default; in a plain run
+               ddp_fastest is that same variant).  With --full the step is also timed once per other exchange variant —
+               bucketed all-reduce or reduce-scatter + sharded Adam + all-gather, collectives issued from the backward hooks
+               or after backward — each over exactly --steps steps (ddp_variants_ms_per_step); the fastest is reported
+               beside the headline (ddp_fastest), never instead of it.  The step with the collectives captured inside the
+               hipGraph is attempted only with DVAE_BENCH_DDP_GRAPH=1.  Diagnostics: rccl_ranks, visible devices, per-rank
+               ms, buckets; with --full allreduce_exposed_ms (step minus the same step with the reducer detached).  With
+               --full the line carries the SAME objects as the N = 1 line: roofline / roofline_lstm (rank 0 alone, reducer
+               detached, after the timed variants), cpu_baseline (after the process group is gone) and scaling_vs_n1
+               (value / the single-rank graph-replayed step timed in the same processes, all ranks at once;
+               DVAE_BENCH_N1_MS supplies a number measured elsewhere).  A
                watchdog over the exchange variants (DVAE_BENCH_VARIANT_TIMEOUT) prints the marked line of what was measured
                if one of them wedges — and then every rank exits 5.
   other_configs  (N=1 only) BASELINE configs[2] (bf16, B=128, T=256) and the per-GPU shape of configs[4] (bf16, B=64,
@@ -317,6 +326,33 @@ def build_trainer(dev, B, T, dtype, world=1, rank=0, force_ddp=False):
     return w
 
 
+DUMP_SAMPLE = 1 << 20     # elements sampled from each flat optimizer buffer for --dump-outputs (4 MB each in fp32)
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, w, losses):
+    """--dump-outputs: what the timed path computed in its LAST timed step, as float32 .npy files (about 16 MB in all):
+      losses.npy          [8]  the loss vector step_async() returned (total, the four L1 terms, the three KL terms)
+      params.npy          the updated parameters (FlatAdam.flat_p), at DUMP_SAMPLE indices drawn with DUMP_SEED
+      exp_avg.npy         Adam's first moment at the same indices (it carries the step's gradient)
+      exp_avg_sq.npy      Adam's second moment at the same indices
+      bn_buffers.npy      every floating-point buffer of the model (BatchNorm running statistics), concatenated
+    The sample depends only on the number of parameters, so it is the same set of elements in every run and build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    opt = w.optimizer
+    n = opt.flat_p.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(opt.flat_p.device)
+    arrays = {"losses": losses.detach().float(),
+              "params": opt.flat_p[idx], "exp_avg": opt.exp_avg[idx], "exp_avg_sq": opt.exp_avg_sq[idx],
+              "bn_buffers": torch.cat([b.detach().reshape(-1).float() for b in w.model.buffers() if b.is_floating_point()])}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    log(f"wrote {', '.join(k + '.npy' for k in arrays)} to {out_dir}")
+
+
 WATCHDOG_RC = 5      # exit code of every rank when the watchdog over the exchange variants fired (a wedged collective)
 L2_CU_TBPS = (17.0, 18.8)     # XCD L2 -> CU delivery, chip-wide (256 CUs x 66-73 GB/s, MI355X_MICROARCH.md)
 LSTM_KINDS = {0: "frame launches, forward", 1: "frame launches, backward", 2: "W_hh-resident persistent launch, forward",
@@ -437,9 +473,14 @@ def main():
                     help="arithmetic of the contractions: fp32x3 (default; fp32 results on the bf16 matrix pipe, the "
                          "headline BASELINE configs[1]), fp32 / f32 (fp32 MFMA), bf16 (configs[2]/[4] semantics; use "
                          "with --batch 128 --frames 256 for configs[2])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: roofline / roofline_lstm, ms_per_step_sync, cpu_baseline, other_configs "
+                         "(N = 1), the other exchange variants and scaling_vs_n1 (N > 1); off: only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: without roofline / roofline_lstm")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: without other_configs")
     ap.add_argument("--graph", type=int, default=1, help="replay the step from a captured hipGraph")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher / rendezvous check only: gloo backend, no GPU work, the line carries dry_launch=true")
@@ -540,15 +581,18 @@ def main():
         for _ in range(max(args.warmup, 2 if use_graph else 0)):   # graph mode: call 1 eager, call 2 captures
             w.step(x1, x2, spk, train=True)
         log("timed region start")
-        elapsed, last, _ = timed(args.steps)
-        last = tuple(last.tolist())
+        elapsed, last_t, _ = timed(args.steps)
+        last = tuple(last_t.tolist())
         ops.lstm_pers_check()
         log(f"timed region done: {1e3 * elapsed / args.steps:.2f} ms/step")
-        n_sync = max(1, min(args.steps, 10))
-        el_sync, _, _ = timed(n_sync, sync_each=True)
-        extra["ms_per_step_sync"] = 1e3 * el_sync / n_sync
-        extra["ms_per_step_sync_note"] = (f"{n_sync} steps through step(): + one device->host copy of the 8 loss scalars and the "
-                                          "persistent-launch error check per step (the reference syncs 8 times per step)")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, w, last_t)
+        if args.full:
+            n_sync = max(1, min(args.steps, 10))
+            el_sync, _, _ = timed(n_sync, sync_each=True)
+            extra["ms_per_step_sync"] = 1e3 * el_sync / n_sync
+            extra["ms_per_step_sync_note"] = (f"{n_sync} steps through step(): + one device->host copy of the 8 loss scalars and "
+                                              "the persistent-launch error check per step (the reference syncs 8 times per step)")
     else:
         # ---------------- data parallel: eager first, then the graph with the collectives captured, if it captures
         log(f"rank {rank}/{world}: model built ({n_params} params), {dtype}, EAGER data-parallel warm-up x{args.warmup}")
@@ -573,6 +617,8 @@ def main():
             w.step(x1, x2, spk, train=True)
         el_e, last, own_e = timed(args.steps)
         fdog.cancel()
+        if args.dump_outputs and rank == 0:      # the replicas hold the same parameters after the exchange
+            dump_outputs(args.dump_outputs, w, last)
         last = tuple(last.tolist())
         ms_eager = 1e3 * el_e / args.steps
         per_rank = torch.zeros(world, device=cdev, dtype=torch.float64)
@@ -627,7 +673,8 @@ def main():
         vdog = threading.Timer(float(os.environ.get("DVAE_BENCH_VARIANT_TIMEOUT", "300")), variants_wedged)
         vdog.daemon = True
         vdog.start()
-        for v in [x for x in want.split(",") if x and x not in variants]:
+        more_variants = [x for x in want.split(",") if x and x not in variants] if args.full else []
+        for v in more_variants:
             wd["now"] = v
             try:
                 mode_v, issue_v = v.split(":")
@@ -695,58 +742,59 @@ def main():
                 w.enable_graph(False)
                 extra["graph_error"] = err or "another rank failed to capture"
             dog.cancel()
-        # exposed communication, measured LAST (the replicas drift apart without the exchange): the same eager step with
-        # the reducer detached, i.e. no collective at all
-        w.enable_graph(False)
-        w.attach_reducer(None)
-        for _ in range(2):
-            w.step_async(x1, x2, spk)
-        n_nr = max(1, min(args.steps, 10))
-        el_nr, _, _ = timed(n_nr)
-        w.attach_reducer(red)
-        extra["ms_per_step_no_allreduce"] = 1e3 * el_nr / n_nr
-        extra["allreduce_exposed_ms"] = ms_eager - 1e3 * el_nr / n_nr
-        extra["allreduce_exposed_variant"] = next(iter(variants))          # the first variant measured (ms_eager)
-        # the single-rank product step (hipGraph replay, no reducer) in THIS process, every rank at once on its own GPU: what
-        # `value` is to be held against (the driver computes the efficiency itself from its own N = 1 run; DVAE_BENCH_N1_MS
-        # supplies a number measured elsewhere instead)
-        n1_ms, n1_src = None, None
-        if os.environ.get("DVAE_BENCH_N1_MS"):
-            n1_ms, n1_src = float(os.environ["DVAE_BENCH_N1_MS"]), "DVAE_BENCH_N1_MS (supplied)"
-        elif args.graph:
-            # the capture may fail on ONE rank: the ranks agree on it (an all-reduce outside the try) BEFORE any of them
-            # enters timed(), whose barriers would otherwise hold the others until the watchdog ends the whole job
-            ok1, err1 = 1, None
-            try:
-                w.attach_reducer(None)
-                w.enable_graph(True)
-                for _ in range(3):
-                    w.step_async(x1, x2, spk)
-                torch.cuda.synchronize()
-            except Exception as e:
-                ok1, err1 = 0, repr(e)[:200]
-            flag1 = torch.tensor([ok1], device=cdev, dtype=torch.int32)
-            dist.all_reduce(flag1, op=dist.ReduceOp.MIN)
-            if int(flag1.item()):
-                el_1, _, _ = timed(n_nr)
-                n1_ms = 1e3 * el_1 / n_nr
-                n1_src = (f"in-process: {n_nr} graph-replayed steps with the reducer detached, all {world} ranks at once "
-                          "(max over ranks)")
-            else:
-                extra["scaling_vs_n1_error"] = err1 or "another rank failed to capture the single-rank step"
+        if args.full:
+            # exposed communication, measured LAST (the replicas drift apart without the exchange): the same eager step with
+            # the reducer detached, i.e. no collective at all
             w.enable_graph(False)
+            w.attach_reducer(None)
+            for _ in range(2):
+                w.step_async(x1, x2, spk)
+            n_nr = max(1, min(args.steps, 10))
+            el_nr, _, _ = timed(n_nr)
             w.attach_reducer(red)
-        if n1_ms:
-            n1_value = B / (n1_ms * 1e-3)
-            extra["scaling_vs_n1"] = {"n1_ms_per_step": n1_ms, "n1_value": n1_value, "source": n1_src,
-                                      "speedup": (world * B * args.steps / elapsed) / n1_value, "ideal": world}
+            extra["ms_per_step_no_allreduce"] = 1e3 * el_nr / n_nr
+            extra["allreduce_exposed_ms"] = ms_eager - 1e3 * el_nr / n_nr
+            extra["allreduce_exposed_variant"] = next(iter(variants))          # the first variant measured (ms_eager)
+            # the single-rank product step (hipGraph replay, no reducer) in THIS process, every rank at once on its own GPU: what
+            # `value` is to be held against (an efficiency against a separate N = 1 run follows from the two lines;
+            # DVAE_BENCH_N1_MS supplies a number measured elsewhere instead)
+            n1_ms, n1_src = None, None
+            if os.environ.get("DVAE_BENCH_N1_MS"):
+                n1_ms, n1_src = float(os.environ["DVAE_BENCH_N1_MS"]), "DVAE_BENCH_N1_MS (supplied)"
+            elif args.graph:
+                # the capture may fail on ONE rank: the ranks agree on it (an all-reduce outside the try) BEFORE any of them
+                # enters timed(), whose barriers would otherwise hold the others until the watchdog ends the whole job
+                ok1, err1 = 1, None
+                try:
+                    w.attach_reducer(None)
+                    w.enable_graph(True)
+                    for _ in range(3):
+                        w.step_async(x1, x2, spk)
+                    torch.cuda.synchronize()
+                except Exception as e:
+                    ok1, err1 = 0, repr(e)[:200]
+                flag1 = torch.tensor([ok1], device=cdev, dtype=torch.int32)
+                dist.all_reduce(flag1, op=dist.ReduceOp.MIN)
+                if int(flag1.item()):
+                    el_1, _, _ = timed(n_nr)
+                    n1_ms = 1e3 * el_1 / n_nr
+                    n1_src = (f"in-process: {n_nr} graph-replayed steps with the reducer detached, all {world} ranks at once "
+                              "(max over ranks)")
+                else:
+                    extra["scaling_vs_n1_error"] = err1 or "another rank failed to capture the single-rank step"
+                w.enable_graph(False)
+                w.attach_reducer(red)
+            if n1_ms:
+                n1_value = B / (n1_ms * 1e-3)
+                extra["scaling_vs_n1"] = {"n1_ms_per_step": n1_ms, "n1_value": n1_value, "source": n1_src,
+                                          "speedup": (world * B * args.steps / elapsed) / n1_value, "ideal": world}
         ops.lstm_pers_check()
         vdog.cancel()
 
     roof = roof_lstm = None
     if dp:
         w.attach_reducer(None)           # the roofline pass below runs on rank 0 alone: no collective in it
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         # the SAME kernels, timed with HIP events around every launch over eager steps right after the timed region
         # (N > 1: rank 0's, with the reducer detached; the other ranks wait in the final barrier)
         prof_steps = min(args.steps, 3)
@@ -794,7 +842,7 @@ def main():
             out["roofline_lstm"] = roof_lstm
         del w
         torch.cuda.empty_cache()
-        if not dp and not args.no_other_configs and (B, T) == (64, 128):
+        if args.full and not dp and not args.no_other_configs and (B, T) == (64, 128):
             others = []
             for name, b, t in (("configs[2]: 1xMI355X bf16, B=128, T=256", 128, 256),
                                ("configs[4] per-GPU shape: bf16, B=64, T=512", 64, 512)):
@@ -808,7 +856,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # (N > 1: after the process group is gone — the other ranks have left, the host cores are free)
             log("timing the CPU oracle on the host cores (child processes, bounded)")
             cb = cpu_baseline(B, T)

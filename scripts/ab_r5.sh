@@ -1,12 +1,14 @@
 #!/bin/bash
 # GPU box, round 6: the round-5 tree and HEAD on the SAME box, back to back.  Prepare in the build container first:
 #   mkdir -p build_exp/r5 && git archive 0a3c193 | tar -x -C build_exp/r5 && (cd build_exp/r5 && bash disentangle-vae-for-vc_amd/csrc/build.sh)
-# (build_exp/ is git-ignored but travels with gpurun)
-(cd build_exp/r5 && timeout 600 python bench.py --no-cpu-baseline > ../../gpurun_out/bench_r5.json 2> ../../gpurun_out/bench_r5.err)
-timeout 900 python bench.py --no-cpu-baseline > gpurun_out/bench_b.json 2> gpurun_out/bench_b.err
+# (build_exp/ is git-ignored; that tree's bench.py always runs the side measurements, HEAD's needs --full).
+#   usage: bash scripts/ab_r5.sh <output directory>
+export OUT="$(mkdir -p "${1:?usage: ab_r5.sh <output directory>}" && cd "$1" && pwd)"
+(cd build_exp/r5 && timeout 600 python bench.py --no-cpu-baseline > "$OUT/bench_r5.json" 2> "$OUT/bench_r5.err")
+timeout 900 python bench.py --full --no-cpu-baseline > "$OUT/bench_b.json" 2> "$OUT/bench_b.err"
 python - <<'PY'
-import json
-for f in ("gpurun_out/bench_r5.json", "gpurun_out/bench_b.json"):
+import json, os
+for f in (os.path.join(os.environ["OUT"], "bench_r5.json"), os.path.join(os.environ["OUT"], "bench_b.json")):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except Exception as e:

@@ -32,7 +32,7 @@ DB4=$(find "$OUT/kt4" -name '*results.db' | head -1)
 if [ -n "$DB4" ]; then python3 scripts/rocpd_stats.py "$DB4" "$SUM/${TAG}_bf16_c4_kernel_stats.csv" 40 > "$SUM/${TAG}_bf16_c4_last_step.txt" 2>&1; fi
 tail -1 "$OUT/kt4.json" > "$SUM/${TAG}_bf16_c4_bench_under_profiler.json"
 # algorithmic bytes per instantiation (bench.py's own tags), for the fabric / algorithmic column of the PMC summary
-python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-other-configs > "$OUT/alg.json" 2> "$OUT/alg.err"
+python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-other-configs > "$OUT/alg.json" 2> "$OUT/alg.err"
 EAGER="bench.py --steps 2 --warmup 1 --graph 0 --no-cpu-baseline --no-other-configs --no-roofline"
 for C in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   D="$OUT/pmc_$(echo $C | tr ' ' '_')"

@@ -16,6 +16,6 @@ mkdir -p gpurun_out
         timeout 300 python scripts/lstm_rec_bench.py 512 0 5 2>&1 | tail -3
     done
   done
-  timeout 600 python bench.py 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'])"
+  timeout 600 python bench.py --full 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench', d['value'], d['ms_per_step'], d['roofline']['frac'])"
 } > gpurun_out/x3h_check.log 2>&1
 tail -60 gpurun_out/x3h_check.log

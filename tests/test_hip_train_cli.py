@@ -88,14 +88,15 @@ def test_train_cli_a_failing_rank_ends_the_job_instead_of_hanging_it(tmp_path):
 
 
 def _bench_two_ranks(env_extra, frames="64", batch="4", rc=0):
-    """`bench.py --gpus 2` as the driver starts it for N = 1 (no rendezvous in the environment: bench.py launches the two
-    ranks itself); the box has one GPU, so the ranks share it and exchange through gloo — a functional check of the N > 1
-    line, not a measurement."""
+    """`bench.py --gpus 2 --full` started without a rendezvous in the environment (bench.py launches the two ranks
+    itself); the box has one GPU, so the ranks share it and exchange through gloo — a functional check of the N > 1
+    line with its side measurements (exchange variants, rooflines, CPU baseline), not a measurement."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", DVAE_ALLOW_SHARED_GPU="1", DVAE_DIST_BACKEND="gloo",
                **env_extra)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--batch", batch, "--frames", frames], env=env, capture_output=True, text=True, timeout=900)
+                        "--batch", batch, "--frames", frames, "--full"], env=env, capture_output=True, text=True,
+                       timeout=900)
     assert r.returncode == rc, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                       # ONE JSON line, from rank 0
@@ -138,3 +139,33 @@ def test_bench_gpus_2_a_wedged_variant_does_not_cost_the_line():
     assert out["n_gpus"] == 2 and out["value"] > 0
     assert "fired during" in out["variant_watchdog"] and out["variant_watchdog_rc"] == 5
     assert "all_reduce:finish" in out["ddp_variants_ms_per_step"]      # the first one measured
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_reproducible_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run times exactly --steps steps and prints the headline alone (the side measurements are
+    --full's); --dump-outputs writes what the last timed step computed, and a second run with the same arguments writes the
+    same arrays: seeded inputs, weights and noise, and a bit-deterministic step."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "4", "--frames", "64", "--dump-outputs", str(d)],
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1
+        assert out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f32" and out["higher_is_better"] is True
+        assert abs(out["value"] - 4 / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+        assert not {"roofline", "roofline_lstm", "ms_per_step_sync", "cpu_baseline", "other_configs"} & set(out), sorted(out)
+        dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+        assert float(dumps[-1]["losses"][0]) == out["final_loss"]
+    assert set(dumps[0]) == {"losses", "params", "exp_avg", "exp_avg_sq", "bn_buffers"}, sorted(dumps[0])
+    assert dumps[0]["losses"].shape == (8,)
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    for k, a in dumps[0].items():
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), k
+        assert np.array_equal(a, dumps[1][k]), k
