@@ -14,6 +14,9 @@ framing+window, magnitude and dB/normalise/transpose are three HBM-bound HIP pas
 The window and the two bases are built on the host in float64 (they are constants of the hyper-parameters):
 `lws` and `librosa` are NOT dependencies — their published constructions are restated here (see oracle/mel_ref.py
 for the parity status of exactly these two pieces).  No CPU fallback: CPU tensors are moved to the device.
+
+`MelInverter` is the way back (normalised mel -> waveform: non-negative mel -> linear solve and fast Griffin-Lim on the
+same window and bases, `inverse_tables`).
 """
 from __future__ import annotations
 
@@ -37,6 +40,35 @@ def _slaney_mel_to_hz(m):
     return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), m * 200.0 / 3.0)
 
 
+def lws_window(fft_size: int, hop_size: int) -> np.ndarray:
+    """lws "speech" analysis (and synthesis) window: sqrt(periodic Hann * 2*hop/fsize), float64 [fsize]."""
+    n = np.arange(fft_size, dtype=np.float64)
+    return np.sqrt((0.5 - 0.5 * np.cos(2.0 * np.pi * n / fft_size)) * 2.0 * hop_size / fft_size)
+
+
+def dft_basis(fft_size: int, nbp: int) -> np.ndarray:
+    """One-sided forward DFT basis, float64 [2*nbp, fsize]: rows [0, nb) cos, rows [nbp, nbp+nb) -sin, padded bins 0."""
+    nb = fft_size // 2 + 1
+    n = np.arange(fft_size, dtype=np.float64)
+    ang = 2.0 * np.pi * np.outer(np.arange(nb, dtype=np.float64), n) / fft_size
+    basis = np.zeros((2 * nbp, fft_size), dtype=np.float64)
+    basis[:nb] = np.cos(ang)
+    basis[nbp:nbp + nb] = -np.sin(ang)
+    return basis
+
+
+def mel_basis(sample_rate: int, fft_size: int, num_mels: int, fmin: float, fmax: float, nbp: int) -> np.ndarray:
+    """librosa.filters.mel (htk=False, Slaney area normalisation), float64 [num_mels, nbp] (padded bins 0)."""
+    nb = fft_size // 2 + 1
+    fft_f = np.linspace(0.0, sample_rate / 2.0, nb)
+    mel_f = _slaney_mel_to_hz(np.linspace(_slaney_hz_to_mel(fmin), _slaney_hz_to_mel(fmax), num_mels + 2))
+    lower = (fft_f[None, :] - mel_f[:-2, None]) / (mel_f[1:-1] - mel_f[:-2])[:, None]
+    upper = (mel_f[2:, None] - fft_f[None, :]) / (mel_f[2:] - mel_f[1:-1])[:, None]
+    melw = np.zeros((num_mels, nbp), dtype=np.float64)
+    melw[:, :nb] = np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (mel_f[2:] - mel_f[:-2]))[:, None]
+    return melw
+
+
 class MelFrontend:
     def __init__(self, device="cuda", sample_rate=16000, fft_size=1024, hop_size=256, num_mels=80, fmin=90.0,
                  fmax=7600.0, min_level_db=-100.0, ref_level_db=16.0):
@@ -52,20 +84,9 @@ class MelFrontend:
         self.min_level = float(np.exp(min_level_db / 20.0 * np.log(10.0)))  # utils.py:128
         nb = fft_size // 2 + 1
         self.nb, self.nbp = nb, (nb + 3) // 4 * 4
-        n = np.arange(fft_size, dtype=np.float64)
-        # lws "speech" analysis window: sqrt(periodic Hann * 2*hop/fsize)
-        win = np.sqrt((0.5 - 0.5 * np.cos(2.0 * np.pi * n / fft_size)) * 2.0 * hop_size / fft_size)
-        ang = 2.0 * np.pi * np.outer(np.arange(nb, dtype=np.float64), n) / fft_size
-        basis = np.zeros((2 * self.nbp, fft_size), dtype=np.float64)
-        basis[:nb] = np.cos(ang)
-        basis[self.nbp:self.nbp + nb] = -np.sin(ang)
-        # librosa.filters.mel (htk=False, Slaney area normalisation)
-        fft_f = np.linspace(0.0, sample_rate / 2.0, nb)
-        mel_f = _slaney_mel_to_hz(np.linspace(_slaney_hz_to_mel(fmin), _slaney_hz_to_mel(fmax), num_mels + 2))
-        lower = (fft_f[None, :] - mel_f[:-2, None]) / (mel_f[1:-1] - mel_f[:-2])[:, None]
-        upper = (mel_f[2:, None] - fft_f[None, :]) / (mel_f[2:] - mel_f[1:-1])[:, None]
-        melw = np.zeros((num_mels, self.nbp), dtype=np.float64)
-        melw[:, :nb] = np.maximum(0.0, np.minimum(lower, upper)) * (2.0 / (mel_f[2:] - mel_f[:-2]))[:, None]
+        win = lws_window(fft_size, hop_size)
+        basis = dft_basis(fft_size, self.nbp)
+        melw = mel_basis(sample_rate, fft_size, num_mels, fmin, fmax, self.nbp)
         f32 = lambda a: torch.from_numpy(a.astype(np.float32)).to(self.device).contiguous()
         self.window, self.dft_basis, self.mel_basis = f32(win), f32(basis), f32(melw)
         self.mode = ops.MODE_F32
@@ -109,3 +130,216 @@ class MelFrontend:
     def melspectrogram(self, wav):
         """One waveform -> [80, M] in [0, 1] (utils.py:68-73)."""
         return self.melspectrogram_batch([wav])[0]
+
+
+# ------------------------------------------------------------------------------------------- inverse (mel -> waveform)
+def inverse_tables(sample_rate=16000, fft_size=1024, hop_size=256, num_mels=80, fmin=90.0, fmax=7600.0) -> dict:
+    """Host-side constants of the Griffin-Lim inverse (float64), built from the same window and mel basis as MelFrontend:
+      window     [fsize]           the lws synthesis window (== analysis window)
+      mel_basis  [num_mels, nbp]   the forward mel projection M
+      inv_basis  [fsize, 2*nbp]    one-sided inverse DFT: y[k] = sum_j c_j/N (Re_j cos - Im_j sin)(2 pi j k / N),
+                                   c_0 = c_{N/2} = 1, c_j = 2 otherwise, padded bins 0
+      pinv       [nbp, num_mels]   pinv(M): the warm start max(0, A pinv^T) of the non-negative mel -> linear solve
+      step       float             1 / ||M||_2^2, the projected-gradient step
+      filt_range [num_mels, 2]     per filter its bin range [lo, hi)
+      bin_filt   [nbp, 2] int32    per bin at most two filters (-1: none) ...
+      bin_w      [nbp, 2]          ... and their weights (Slaney triangles overlap their neighbours only)
+      ola_norm   bool              the squared window does NOT overlap-add to 1 at this hop: divide by the envelope"""
+    nb = fft_size // 2 + 1
+    nbp = (nb + 3) // 4 * 4
+    win = lws_window(fft_size, hop_size)
+    melw = mel_basis(sample_rate, fft_size, num_mels, fmin, fmax, nbp)
+    k = np.arange(fft_size, dtype=np.float64)
+    ang = 2.0 * np.pi * np.outer(k, np.arange(nb, dtype=np.float64)) / fft_size      # [fsize, nb]
+    c = np.full(nb, 2.0)
+    c[0] = 1.0
+    if fft_size % 2 == 0:
+        c[-1] = 1.0
+    inv = np.zeros((fft_size, 2 * nbp), dtype=np.float64)
+    inv[:, :nb] = c / fft_size * np.cos(ang)
+    inv[:, nbp:nbp + nb] = -c / fft_size * np.sin(ang)
+    pinv = np.linalg.pinv(melw)
+    step = 1.0 / float(np.linalg.norm(melw, 2)) ** 2
+    rng = np.zeros((num_mels, 2), dtype=np.int32)
+    bin_filt = np.full((nbp, 2), -1, dtype=np.int32)
+    bin_w = np.zeros((nbp, 2), dtype=np.float64)
+    cnt = np.zeros(nbp, dtype=np.int64)
+    for f in range(num_mels):
+        nz = np.nonzero(melw[f])[0]
+        if nz.size:
+            rng[f] = (nz[0], nz[-1] + 1)
+            assert np.all(melw[f, nz[0]:nz[-1] + 1] > 0), "a mel filter with a gap"
+        for j in nz:
+            assert cnt[j] < 2, f"bin {j} under more than two mel filters"
+            bin_filt[j, cnt[j]], bin_w[j, cnt[j]] = f, melw[f, j]
+            cnt[j] += 1
+    if fft_size % hop_size:
+        raise ValueError("inverse_tables: fft_size must be a multiple of hop_size")
+    # steady-state overlap-add of the squared window (every output sample of the inverse is in the steady state, see
+    # MelInverter): 1 for the lws window at hop = fsize/4, so the defaults need no division
+    env = (win ** 2).reshape(fft_size // hop_size, hop_size).sum(0)
+    ola_norm = not np.allclose(env, 1.0, rtol=0, atol=1e-12)
+    return dict(window=win, mel_basis=melw, inv_basis=inv, pinv=pinv, step=step, filt_range=rng, bin_filt=bin_filt,
+                bin_w=bin_w, ola_norm=ola_norm, nb=nb, nbp=nbp)
+
+
+class MelInverter:
+    """Normalised mel [80, M] -> waveform of n = (M - 3) * hop samples (lws_num_frames(n) == M), on the GPU:
+
+      amplitude   A = 10^((clip(S, 0, 1) * 100 - 100 + 16) / 20), frame-major       (dvae_mel_denormalize)
+      magnitude   X = max(0, A pinv(M)^T), then `nnls_iter` projected-gradient steps
+                  X <- max(0, X - eta M^T (M X - A)), one frame per workgroup on chip   (dvae_gemm_f32 + dvae_mel_nnls_pg)
+      phase       fast Griffin-Lim (librosa.griffinlim, momentum 0.99) from a random, zero or given phase; per iteration
+                  inverse DFT [rows, 2*nbp] x [fsize, 2*nbp]^T, overlap-add + re-framing gather, forward DFT
+                  [rows, fsize] x [2*nbp, fsize]^T, fused phase update: four launches for the whole batch
+      waveform    a last inverse DFT and the overlap-add gather into the packed output
+
+    The intent of the reference's `simple_inverse` (preprocessing/processing.py:133-139) carried out properly: the front-end
+    the corpus was made with is inverted, dB normalisation included.  A batch of utterances of different lengths is packed
+    row-wise; only the overlap-add crosses rows, through a small device segment table.  Both DFT contractions are pinned
+    to fp32 products and an unsplit k (a row's result does not depend on the training compute mode, the deterministic
+    switch or what else shares the batch).  GPU only, no CPU fallback."""
+
+    def __init__(self, device="cuda", sample_rate=16000, fft_size=1024, hop_size=256, num_mels=80, fmin=90.0,
+                 fmax=7600.0, min_level_db=-100.0, ref_level_db=16.0, n_iter=32, momentum=0.99, nnls_iter=200):
+        if fft_size % 4 or hop_size % 4 or hop_size < 4 or hop_size > fft_size or fft_size % hop_size:
+            raise ValueError("MelInverter: fft_size and hop_size must be multiples of 4, fft_size a multiple of hop_size")
+        if not fmax <= sample_rate / 2:
+            raise ValueError("MelInverter: fmax above Nyquist")
+        if not min_level_db < 0:
+            raise ValueError("MelInverter: min_level_db must be negative")
+        if n_iter < 0 or nnls_iter < 0 or not 0.0 <= momentum:
+            raise ValueError("MelInverter: n_iter, nnls_iter and momentum must be >= 0")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("MelInverter runs on the HIP path only (no CPU fallback)")
+        self.sr, self.fsize, self.hop, self.n_mels = sample_rate, fft_size, hop_size, num_mels
+        self.min_level_db, self.ref_level_db = float(min_level_db), float(ref_level_db)
+        self.n_iter, self.momentum, self.nnls_iter = int(n_iter), float(momentum), int(nnls_iter)
+        self.min_frames = fft_size // hop_size
+        t = inverse_tables(sample_rate, fft_size, hop_size, num_mels, fmin, fmax)
+        self.nb, self.nbp, self.step, self.ola_norm = t["nb"], t["nbp"], float(t["step"]), int(t["ola_norm"])
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        self.window, self.inv_basis, self.pinv = f32(t["window"]), f32(t["inv_basis"]), f32(t["pinv"])
+        self.dft_basis = f32(dft_basis(fft_size, self.nbp))
+        self.filt_range, self.bin_filt, self.bin_w = i32(t["filt_range"]), i32(t["bin_filt"]), f32(t["bin_w"])
+        self.mode = ops.MODE_F32
+
+    def num_samples(self, frames: int) -> int:
+        """M frames -> n samples, with lws_num_frames(n) == M"""
+        return (frames - self.min_frames + 1) * self.hop
+
+    def _frames_of(self, counts):
+        if not counts:
+            raise ValueError("MelInverter: empty batch")
+        bad = [m for m in counts if m < self.min_frames]
+        if bad:
+            raise ValueError(f"MelInverter: {bad[0]} frames; the inverse needs >= {self.min_frames} (fft_size / hop_size)")
+
+    def _gemm(self, A, B, C, K, act=ops.ACT_NONE):
+        # C[rows, N] = act(A[rows, K] B[N, K]^T): fp32 products, ONE k-split whatever the row count (bits of a row
+        # independent of the batch it shares a launch with, of the compute mode and of ops.set_deterministic)
+        ops.gemm(A, B, C, None, A.shape[0], B.shape[0], K, K, K, B.shape[0], True, True, act, ops.EPI_STORE, 1, self.mode)
+
+    def _magnitude(self, mels):
+        """list of [80, M_i] -> (X [rows, nbp] device, [M_i])"""
+        L = lib()
+        ms = [torch.as_tensor(m).to(self.device, torch.float32) for m in mels]
+        if any(m.dim() != 2 or m.shape[0] != self.n_mels for m in ms):
+            raise ValueError(f"MelInverter: mels must be [{self.n_mels}, M]")
+        counts = [int(m.shape[1]) for m in ms]
+        self._frames_of(counts)
+        mel = torch.cat(ms, dim=1).contiguous() if len(ms) > 1 else ms[0].contiguous()
+        rows = mel.shape[1]
+        amp = torch.empty((rows, self.n_mels), device=self.device, dtype=torch.float32)
+        check(L.dvae_mel_denormalize(ptr(mel), ptr(amp), rows, self.n_mels, rows, self.ref_level_db, self.min_level_db,
+                                     stream()), "dvae_mel_denormalize")
+        x = torch.empty((rows, self.nbp), device=self.device, dtype=torch.float32)
+        self._gemm(amp, self.pinv, x, self.n_mels, act=ops.ACT_RELU)
+        check(L.dvae_mel_nnls_pg(ptr(amp), ptr(x), rows, self.nbp, self.n_mels, ptr(self.filt_range), ptr(self.bin_filt),
+                                 ptr(self.bin_w), self.step, self.nnls_iter, stream()), "dvae_mel_nnls_pg")
+        return x, counts
+
+    def linear_magnitude_batch(self, mels: Sequence) -> list:
+        """list of [80, M_i] normalised mels -> list of device tensors [M_i, fft_size//2 + 1] (frame-major |STFT|)"""
+        x, counts = self._magnitude(mels)
+        out, r = [], 0
+        for m in counts:
+            out.append(x[r:r + m, :self.nb])
+            r += m
+        return out
+
+    def griffinlim_batch(self, mags: Sequence, n_iter=None, init="random", generator=None, init_phase=None) -> list:
+        """list of [M_i, nb] (or [M_i, nbp]) linear magnitudes -> list of 1-D device waveforms of num_samples(M_i).
+        init: "random" (uniform phase from `generator`, or the device's default generator) | "zeros"; init_phase: list of
+        [M_i, nb] phases in radians (overrides `init`)."""
+        L = lib()
+        n_iter = self.n_iter if n_iter is None else int(n_iter)
+        if n_iter < 0:
+            raise ValueError("MelInverter: n_iter must be >= 0")
+        ms = [torch.as_tensor(m).to(self.device, torch.float32) for m in mags]
+        counts = [int(m.shape[0]) for m in ms]
+        self._frames_of(counts)
+        rows, nbp, fs = sum(counts), self.nbp, self.fsize
+        S = torch.zeros((rows, nbp), device=self.device, dtype=torch.float32)
+        r = 0
+        for m, c in zip(ms, counts):
+            if m.dim() != 2 or m.shape[1] not in (self.nb, nbp):
+                raise ValueError(f"MelInverter: magnitudes must be [M, {self.nb}]")
+            S[r:r + c, :m.shape[1]] = m
+            r += c
+        phase = None
+        if init_phase is not None:
+            phase = torch.zeros((rows, nbp), device=self.device, dtype=torch.float32)
+            r = 0
+            for p, c in zip(init_phase, counts):
+                p = torch.as_tensor(p).to(self.device, torch.float32)
+                if p.shape[0] != c:
+                    raise ValueError("MelInverter: init_phase rows differ from the magnitudes'")
+                phase[r:r + c, :p.shape[1]] = p
+                r += c
+        elif init == "random":
+            gdev = generator.device if generator is not None else self.device
+            phase = (2.0 * math.pi) * torch.rand((rows, nbp), generator=generator, device=gdev, dtype=torch.float32)
+            phase = phase.to(self.device)
+        elif init != "zeros":
+            raise ValueError(f"MelInverter: init={init!r}, expected 'random' or 'zeros'")
+        table = np.zeros((len(counts), 4), dtype=np.int64)
+        cnt = np.asarray(counts, dtype=np.int32)
+        check(L.dvae_gl_segment_table(cnt.ctypes.data, len(counts), fs, self.hop, table.ctypes.data),
+              "dvae_gl_segment_table")
+        segs = torch.from_numpy(table).to(self.device)
+        n_total = int(table[-1, 2] + table[-1, 3])
+        X = torch.empty((rows, 2 * nbp), device=self.device, dtype=torch.float32)
+        check(L.dvae_gl_init(ptr(S), ptr(phase), ptr(X), rows, nbp, stream()), "dvae_gl_init")
+        y = torch.empty((rows, fs), device=self.device, dtype=torch.float32)
+        frames = torch.empty_like(y)
+        reb, prev = torch.empty_like(X), torch.empty_like(X)
+        nseg = len(counts)
+        for it in range(n_iter):
+            self._gemm(X, self.inv_basis, y, 2 * nbp)
+            check(L.dvae_ola_gather(ptr(y), ptr(segs), nseg, rows, ptr(self.window), ptr(frames), 0, fs, self.hop, 0,
+                                    self.ola_norm, stream()), "dvae_ola_gather")
+            self._gemm(frames, self.dft_basis, reb, fs)
+            check(L.dvae_gl_phase(ptr(reb), ptr(prev) if it else None, ptr(S), ptr(X), rows, nbp, self.momentum, stream()),
+                  "dvae_gl_phase")
+            reb, prev = prev, reb
+        self._gemm(X, self.inv_basis, y, 2 * nbp)
+        wav = torch.empty(n_total, device=self.device, dtype=torch.float32)
+        check(L.dvae_ola_gather(ptr(y), ptr(segs), nseg, rows, ptr(self.window), ptr(wav), n_total, fs, self.hop, 1,
+                                self.ola_norm, stream()), "dvae_ola_gather")
+        return [wav[int(s0):int(s0 + n)] for s0, n in zip(table[:, 2], table[:, 3])]
+
+    def waveform_batch(self, mels: Sequence, n_iter=None, init="random", generator=None, init_phase=None) -> list:
+        """list of [80, M_i] normalised mels (the corpus layout) -> list of 1-D device waveforms of (M_i - 3) * hop samples"""
+        x, counts = self._magnitude(mels)
+        out, r = [], 0
+        for m in counts:
+            out.append(x[r:r + m])
+            r += m
+        return self.griffinlim_batch(out, n_iter=n_iter, init=init, generator=generator, init_phase=init_phase)
+
+    def waveform(self, mel, **kw):
+        """One [80, M] mel -> 1-D device waveform"""
+        return self.waveform_batch([mel], **kw)[0]

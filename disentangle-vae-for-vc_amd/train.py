@@ -7,7 +7,12 @@ Kept flags: --batch-size --latent-size --speaker_size --lr --epochs --report-int
 --dataset_fp --log_dir --train --samples_length (honoured here; the reference parses it but hard-codes 64,
 train.py:53).  Parsed-and-ignored flags of the reference (--hidden-size --alpha --normalize --beta_cof --style_cof
 --sample-size --no-cuda --do-not-resume --log-interval) are accepted for command-line compatibility.
---convert (voice conversion + vocoder) is out of scope.
+--convert (reference variational_base_vae.py:243-330, minus plots): the first --convert-count sorted utterances of
+--src_spk, each with a random utterance of --trg_spk (seeded by --seed), through `convert_mel`; the converted mels are
+voiced by the GPU Griffin-Lim inverse of the mel front-end (frontend.MelInverter, --griffin-lim-iters) instead of the
+reference's WaveNet, whose code and weights are not part of the reference, and written to
+<log_dir>/generation/<src>_to_<trg>/convert_<src>_to_<trg>_<utt>.wav (16 kHz mono PCM-16) with the source, reconstructed
+and converted mels as .npy.
 
 Data parallel (new; the reference is single-device, train.py:49-58): started as one of WORLD_SIZE > 1 ranks —
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 -m dvae_amd.train ...` or with
@@ -52,6 +57,10 @@ def get_parse():
     p.add_argument("--log_dir", default="./results", type=str)
     p.add_argument("--train", type=bool, default=False)
     p.add_argument("--convert", type=bool, default=False)
+    p.add_argument("--src_spk", default="VCTK-Corpus_wav16_p225", type=str)
+    p.add_argument("--trg_spk", default="VCTK-Corpus_wav16_p226", type=str)
+    p.add_argument("--convert-count", type=int, default=2, help="--convert: the first N sorted utterances of --src_spk")
+    p.add_argument("--griffin-lim-iters", type=int, default=32, help="--convert: Griffin-Lim iterations of the vocoder")
     p.add_argument("--graph", type=int, default=1, help="replay the step from a hipGraph (fixed batch shape)")
     p.add_argument("--gpus", type=int, default=0,
                    help="data-parallel ranks on this node; > 1 without WORLD_SIZE in the environment: launch them")
@@ -151,6 +160,63 @@ def _abort_process_group():
         pass
 
 
+def utterance_id(path: str) -> str:
+    """reference variational_base_vae.py:275: `<anything>_<utt>_<suffix>.npy` -> <utt>"""
+    parts = os.path.basename(path).split(".")[0].split("_")
+    return parts[-2] if len(parts) >= 2 else parts[0]
+
+
+def write_wav(path: str, wav, sample_rate: int = 16000):
+    """mono PCM-16 .wav (soundfile's default subtype for .wav), samples clipped to [-1, 1]"""
+    import wave
+
+    import numpy as np
+    x = np.clip(np.asarray(wav, dtype=np.float64), -1.0, 1.0)
+    pcm = np.round(x * 32767.0).astype("<i2")
+    with wave.open(path, "wb") as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(sample_rate)
+        w.writeframes(pcm.tobytes())
+
+
+def convert(vsc, args, logging_func=print):
+    """--convert: reference voice_conversion_mel (variational_base_vae.py:243-330) with the Griffin-Lim vocoder"""
+    from glob import glob
+
+    import numpy as np
+
+    from .frontend import MelInverter
+    src, trg = args.src_spk, args.trg_spk
+    save_dir = os.path.join(args.log_dir, "generation", f"{src}_to_{trg}")
+    os.makedirs(save_dir, exist_ok=True)
+    vsc.load_last_model(os.path.join(args.log_dir, "checkpoints"), logging_func=logging_func)
+    sources = sorted(glob(os.path.join(args.dataset_fp, src, "*.npy")))[:args.convert_count]
+    targets = sorted(glob(os.path.join(args.dataset_fp, trg, "*.npy")))
+    if not sources or not targets:
+        raise SystemExit(f"--convert: no .npy utterances under {args.dataset_fp}/{src} or {args.dataset_fp}/{trg}")
+    rng = np.random.RandomState(args.seed)
+    names, converted = [], []
+    for fp in sources:
+        t = targets[rng.randint(len(targets))]
+        utt = utterance_id(fp)
+        logging_func(f"convert utterance: {utt} from --->{src} to --->{trg}")
+        out = vsc.convert_mel(np.load(fp), np.load(t))
+        np.save(os.path.join(save_dir, f"source_{src}_{utt}.npy"), out["source"].cpu().numpy())
+        np.save(os.path.join(save_dir, f"recons_{src}_{utt}.npy"), out["recons"].cpu().numpy())
+        np.save(os.path.join(save_dir, f"convert_{src}_to_{trg}_{utt}.npy"), out["converted"].cpu().numpy())
+        names.append(f"convert_{src}_to_{trg}_{utt}.wav")
+        converted.append(out["converted"])
+    inv = MelInverter(device=vsc.device)
+    gen = torch.Generator(device=vsc.device)
+    gen.manual_seed(args.seed)
+    wavs = inv.waveform_batch(converted, n_iter=args.griffin_lim_iters, generator=gen)
+    for name, w in zip(names, wavs):
+        write_wav(os.path.join(save_dir, name), w.cpu().numpy(), inv.sr)
+        logging_func(f"wrote {os.path.join(save_dir, name)}")
+    return [os.path.join(save_dir, n) for n in names]
+
+
 def main(argv=None):
     args = get_parse().parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -208,8 +274,8 @@ def main(argv=None):
                                     images_path=os.path.join(args.log_dir, "images"),
                                     logs_path=os.path.join(args.log_dir, "logs"),
                                     estimation_dir=os.path.join(args.log_dir, "images", "estimation"))
-        if args.convert:
-            raise SystemExit("--convert (mel conversion + vocoder) is outside the training hot path (SURVEY.md §8f-3)")
+        if args.convert and rank == 0:
+            convert(vsc, args)
     except BaseException:
         # A rank that FAILS must not enter a barrier: its peers are inside an all-reduce / reduce-scatter, not a barrier, and
         # the mismatched collective would hold this rank (and its traceback) until the RCCL timeout.  Tear the group down

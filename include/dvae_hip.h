@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 307
+#define DVAE_ABI_VERSION 308
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -452,6 +452,32 @@ int dvae_stft_frames(const float* wav, int64_t n, const float* window, float* fr
 int dvae_stft_magnitude(const float* reim, float* mag, int64_t rows, int nbins_padded, void* stream);
 int dvae_mel_db_normalize(const float* mel, float* out, int M, int n_mels, int64_t ld_out, int64_t col0,
                           float min_level, float ref_level_db, float min_level_db, void* stream);
+
+/* ---- Griffin-Lim inverse of the mel front-end (frontend.py MelInverter): normalised mel -> amplitude -> non-negative
+ * linear magnitude -> fast Griffin-Lim -> waveform.  Every frame of every utterance of a batch is one row; the two DFT
+ * contractions per iteration are dvae_gemm_f32 launches (fp32, unsplit); these are the passes around them.
+ * dvae_mel_denormalize: mel[n_mels, ld_in] (columns 0..L) -> amp[L, n_mels] = 10^((clip(mel,0,1) * -min_db + min_db + ref_db) / 20).
+ * dvae_mel_nnls_pg: x[rows, nbp] (in: warm start, out: solution) <- `iters` projected-gradient steps
+ *   x = max(0, x - step * M^T (M x - amp)), M given sparsely: filt_range[n_mels][2] = bin range [lo, hi) of each filter,
+ *   bin_filt[nbp][2] / bin_w[nbp][2] = the (at most two) filters of each bin (-1: none).  nbp <= 1024, n_mels <= 128.
+ * dvae_gl_init: reim[rows, 2*nbp] (real block | imaginary block) = mag * exp(i phase); phase NULL: zero phase.
+ * dvae_gl_phase: a = rebuilt - momentum/(1+momentum) * prev (prev NULL: 0), reim = mag * a / |a| (mag where |a| = 0).
+ * dvae_gl_segment_table (host): table[nseg][4] = {row0, frames M, sample0, n = (M - fsize/hop + 1) * hop} of utterances
+ *   packed row-wise; DVAE_EINVAL when some M < fsize/hop, fsize % hop != 0, or hop / fsize not multiples of 4.
+ * dvae_ola_gather: overlap-add of the synthesis frames y[rows, fsize] with `window` inside each segment (`segs`: the table
+ *   above, in device memory); mode 0: out[rows, fsize] = the next windowed analysis frames of the length-n signals (zero
+ *   outside [0, n)); mode 1: out[sample0 + t] = sample t, out_len = total samples.  norm: divide by the overlap-added
+ *   squared window. */
+int dvae_mel_denormalize(const float* mel, float* amp, int L, int n_mels, int64_t ld_in, float ref_level_db,
+                         float min_level_db, void* stream);
+int dvae_mel_nnls_pg(const float* amp, float* x, int64_t rows, int nbp, int n_mels, const int* filt_range,
+                     const int* bin_filt, const float* bin_w, float step, int iters, void* stream);
+int dvae_gl_init(const float* mag, const float* phase, float* reim, int64_t rows, int nbp, void* stream);
+int dvae_gl_phase(const float* rebuilt, const float* prev, const float* mag, float* reim, int64_t rows, int nbp,
+                  float momentum, void* stream);
+int dvae_gl_segment_table(const int* frames, int nseg, int fsize, int hop, int64_t* table);
+int dvae_ola_gather(const float* y, const int64_t* segs, int nseg, int64_t rows, const float* window, float* out,
+                    int64_t out_len, int fsize, int hop, int mode, int norm, void* stream);
 
 /* ---- opt-in per-family kernel timing with HIP events on the launch stream (bench.py roofline) ----
  * family: 0 = off, 1 = GEMM/conv contraction kernel, 2 = LSTM step kernels.
