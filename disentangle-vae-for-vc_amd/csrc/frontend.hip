@@ -259,6 +259,190 @@ __global__ void ola_gather_kernel(const float* __restrict__ y, const int64_t* __
   }
 }
 
+
+// ---- corpus preprocessing (preprocessing/encoder/audio.py:22-51 `preprocess_wav`): band-limited resampling (resampy
+// kaiser_best), increase-only volume normalisation, and the framing / dB passes of the mel path on a PACKED batch
+// (one launch per pass for the whole batch; an element's bits depend only on its own utterance).
+
+// segment row {in0, n_in, out0, n_out, n_valid, filter} (int64 x 6), filter row {P, Q, taps, base, woff, -} (int64 x 6),
+// tile row {segment, t0} (int64 x 2).  Output t < n_valid of a segment: m = floor(t Q / P), phase = t Q - m P,
+// y[t] = sum_{c < taps} w[woff + phase*taps + c] * x[m - base + c] (x zero outside [0, n_in)); t >= n_valid: 0.
+constexpr int RS_TILE = 256;                                 // DVAE_RESAMPLE_TILE
+__global__ void __launch_bounds__(RS_TILE) resample_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                          const int64_t* __restrict__ segs,
+                                                          const int64_t* __restrict__ filts,
+                                                          const float* __restrict__ w,
+                                                          const int64_t* __restrict__ tiles, int lds_cap) {
+  extern __shared__ float xs[];
+  const int tid = threadIdx.x;
+  const int64_t sg = tiles[2 * blockIdx.x], t0 = tiles[2 * blockIdx.x + 1];
+  const int64_t* s = segs + 6 * sg;
+  const int64_t in0 = s[0], n_in = s[1], out0 = s[2], n_out = s[3], n_valid = s[4];
+  const int64_t* f = filts + 6 * s[5];
+  const int64_t P = f[0], Q = f[1], base = f[3], woff = f[4];
+  const int taps = (int)f[2];
+  const int64_t t_end = min(t0 + RS_TILE, n_valid);          // outputs [t0, t_end) run the filter
+  if (t0 < t_end) {
+    const int64_t lo = (t0 * Q) / P - base;                  // first input sample of the tile's span
+    const int64_t hi = ((t_end - 1) * Q) / P - base + taps;  // one past the last
+    const int64_t g0 = in0 + lo;                             // packed index of xs[shift]
+    const int64_t a0 = g0 & ~(int64_t)3;                    // floor to a 16-byte boundary (g0 may be < 0)
+    const int shift = (int)(g0 - a0);
+    const int nld = min((int)(hi - lo) + shift, lds_cap);
+    const int64_t s_lo = in0, s_hi = in0 + n_in;             // valid packed range of this segment
+    for (int q = tid * 4; q < nld; q += RS_TILE * 4) {
+      const int64_t g = a0 + q;
+      f32x4 v;
+      if (g >= s_lo && g + 3 < s_hi) {
+        v = *reinterpret_cast<const f32x4*>(x + g);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (g + e >= s_lo && g + e < s_hi) ? x[g + e] : 0.f;
+      }
+      if (q + 3 < lds_cap) {
+        *reinterpret_cast<f32x4*>(xs + q) = v;
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (q + e < lds_cap) xs[q + e] = v[e];
+      }
+    }
+    __syncthreads();
+    const int64_t t = t0 + tid;
+    if (t < t_end) {
+      const int64_t m = (t * Q) / P, ph = t * Q - m * P;
+      const int j0 = (int)(m - base - lo) + shift;
+      const float* __restrict__ wr = w + woff + ph * taps;
+      float acc = 0.f;
+      if (j0 >= 0 && j0 + taps <= lds_cap) {
+        for (int c = 0; c < taps; ++c) acc = fmaf(wr[c], xs[j0 + c], acc);
+      } else {
+        acc = __builtin_nanf("");                            // the host's LDS bound was wrong: never silently
+      }
+      y[out0 + t] = acc;
+    }
+  }
+  const int64_t t = t0 + tid;
+  if (t >= n_valid && t < min(t0 + RS_TILE, n_out)) y[out0 + t] = 0.f;   // librosa fix=True pad
+}
+
+// volume: per tile of NV_TILE samples sum of squares in float64 (each thread its 8 samples in order, then a fixed tree)
+constexpr int NV_THREADS = 256, NV_PER = 8, NV_TILE = NV_THREADS * NV_PER;
+static_assert(NV_TILE == 2048 && RS_TILE == 256, "DVAE_VOLUME_TILE / DVAE_RESAMPLE_TILE of include/dvae_hip.h");
+__global__ void __launch_bounds__(NV_THREADS) sumsq_tiles_kernel(const float* __restrict__ y,
+                                                                const int64_t* __restrict__ segs,
+                                                                const int64_t* __restrict__ tiles,
+                                                                double* __restrict__ part) {
+  __shared__ double red[NV_THREADS];
+  const int tid = threadIdx.x;
+  const int64_t sg = tiles[2 * blockIdx.x], t0 = tiles[2 * blockIdx.x + 1];
+  const int64_t out0 = segs[6 * sg + 2], n_out = segs[6 * sg + 3];
+  double acc = 0.0;
+#pragma unroll
+  for (int e = 0; e < NV_PER; ++e) {
+    const int64_t t = t0 + (int64_t)tid * NV_PER + e;
+    if (t < n_out) {
+      const double v = (double)y[out0 + t];
+      acc += v * v;
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int h = NV_THREADS / 2; h > 0; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) part[blockIdx.x] = red[0];
+}
+
+// one thread per segment: mean square from its tiles' partials (tile_first[s] .. tile_first[s+1]) in order, then the gain
+// of normalize_volume (audio.py:121-127): change = target - 10 log10(ms); increase_only and change < 0 -> 1
+__global__ void volume_finalize_kernel(const int64_t* __restrict__ segs, int nseg, const int64_t* __restrict__ tile_first,
+                                       const double* __restrict__ part, double target_dbfs, int increase_only,
+                                       double* __restrict__ ms_out, float* __restrict__ gain, int* __restrict__ silent) {
+  const int sg = blockIdx.x * blockDim.x + threadIdx.x;
+  if (sg >= nseg) return;
+  double sum = 0.0;
+  for (int64_t i = tile_first[sg]; i < tile_first[sg + 1]; ++i) sum += part[i];
+  const int64_t n = segs[6 * sg + 3];
+  const double ms = n > 0 ? sum / (double)n : 0.0;
+  float g = 1.f;
+  int sil = 0;
+  if (!(ms > 0.0)) {
+    sil = 1;                                     // the reference: 0 * 10^(inf) = NaN mel; here flagged, left as is
+  } else {
+    const double change = target_dbfs - 10.0 * log10(ms);
+    if (!(increase_only && change < 0.0)) g = (float)pow(10.0, change / 20.0);
+  }
+  if (ms_out) ms_out[sg] = ms;
+  gain[sg] = g;
+  silent[sg] = sil;
+}
+
+__global__ void __launch_bounds__(NV_THREADS) volume_scale_kernel(float* __restrict__ y, const int64_t* __restrict__ segs,
+                                                                 const int64_t* __restrict__ tiles,
+                                                                 const float* __restrict__ gain) {
+  const int64_t sg = tiles[2 * blockIdx.x], t0 = tiles[2 * blockIdx.x + 1];
+  const float g = gain[sg];
+  if (g == 1.f) return;
+  const int64_t out0 = segs[6 * sg + 2], n_out = segs[6 * sg + 3];
+#pragma unroll
+  for (int e = 0; e < NV_PER; ++e) {
+    const int64_t t = t0 + (int64_t)e * NV_THREADS + threadIdx.x;
+    if (t < n_out) y[out0 + t] = y[out0 + t] * g;
+  }
+}
+
+// stft_frames_kernel over a packed batch: row r of segment {row0, M, sample0, n} (the dvae_gl_segment_table layout) is
+// frame r - row0 of the signal wav[sample0, sample0 + n): the same expression per element
+__global__ void stft_frames_seg_kernel(const float* __restrict__ wav, const int64_t* __restrict__ segs, int nseg,
+                                       int64_t rows, const float* __restrict__ win, float* __restrict__ frames, int fsize,
+                                       int hop, int left) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per_row = fsize >> 2;
+  if (idx >= rows * per_row) return;
+  const int64_t r = idx / per_row;
+  const int k = ((int)(idx - r * per_row)) << 2;
+  const int sg = find_segment(segs, nseg, r, 0);
+  const int64_t row0 = segs[4 * sg], sample0 = segs[4 * sg + 2], n = segs[4 * sg + 3];
+  const int64_t s = (r - row0) * hop + k - left;
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int64_t i = s + e;
+    v[e] = (i >= 0 && i < n) ? wav[sample0 + i] * win[k + e] : 0.f;
+  }
+  *reinterpret_cast<f32x4*>(frames + r * fsize + k) = v;
+}
+
+// mel_db_normalize_kernel over a packed batch: mel[rows, C] -> out = the utterances' [C, M] blocks back to back (segment
+// s at C * row0), the same expression per element
+__global__ void mel_db_normalize_seg_kernel(const float* __restrict__ mel, float* __restrict__ out,
+                                            const int64_t* __restrict__ segs, int nseg, int64_t rows, int C,
+                                            float min_level, float ref_db, float min_db) {
+  __shared__ float tile[32][33];
+  const int64_t m0 = (int64_t)blockIdx.x * 32;
+  const int c0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int r = ty; r < 32; r += 8) {
+    const int64_t m = m0 + r;
+    const int c = c0 + tx;
+    tile[r][tx] = (m < rows && c < C) ? mel[m * C + c] : 1.f;
+  }
+  __syncthreads();
+  const int64_t m = m0 + tx;
+  if (m >= rows) return;
+  const int sg = find_segment(segs, nseg, m, 0);
+  const int64_t row0 = segs[4 * sg], M = segs[4 * sg + 1];
+  for (int r = ty; r < 32; r += 8) {
+    const int c = c0 + r;
+    if (c < C) {
+      const float db = 20.f * log10f(fmaxf(min_level, tile[tx][r])) - ref_db;
+      out[C * row0 + (int64_t)c * M + (m - row0)] = fminf(fmaxf((db - min_db) / -min_db, 0.f), 1.f);
+    }
+  }
+}
+
 }  // namespace
 
 DVAE_API int dvae_stft_frames(const float* wav, int64_t n, const float* window, float* frames, int M, int fsize,
@@ -352,5 +536,97 @@ DVAE_API int dvae_ola_gather(const float* y, const int64_t* segs, int nseg, int6
   const int64_t work = mode == 0 ? rows * (fsize >> 2) : (out_len >> 2);
   hipLaunchKernelGGL(ola_gather_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, segs,
                      nseg, rows, window, out, out_len, fsize, hop, mode, norm);
+  return dvae_check_launch();
+}
+
+
+// ---- corpus preprocessing
+DVAE_API int dvae_resample_segment_table(const int64_t* n_in, const int* filt, int nseg, const int64_t* filters, int nfilt,
+                                         int tile, int64_t* table, int64_t* tiles, int64_t max_tiles) {
+  if (!n_in || !filt || !filters || !table || nseg < 1 || nfilt < 1 || tile < 1) return DVAE_EINVAL;
+  int64_t in0 = 0, out0 = 0, nt = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const int f = filt[s];
+    if (f < 0 || f >= nfilt || n_in[s] < 1) return DVAE_EINVAL;
+    const int64_t P = filters[6 * f], Q = filters[6 * f + 1];
+    if (P < 1 || Q < 1 || n_in[s] > ((int64_t)1 << 40) / (P > Q ? P : Q)) return DVAE_EINVAL;
+    const int64_t n_valid = n_in[s] * P / Q;              // resampy: int(n * ratio)
+    const int64_t n_out = (n_in[s] * P + Q - 1) / Q;      // librosa fix=True: ceil(n * ratio)
+    if (n_valid < 1) return DVAE_EINVAL;                  // resampy raises
+    int64_t* r = table + 6 * s;
+    r[0] = in0;
+    r[1] = n_in[s];
+    r[2] = out0;
+    r[3] = n_out;
+    r[4] = n_valid;
+    r[5] = f;
+    for (int64_t t0 = 0; t0 < n_out; t0 += tile, ++nt) {
+      if (tiles) {
+        if (nt >= max_tiles) return DVAE_EINVAL;
+        tiles[2 * nt] = s;
+        tiles[2 * nt + 1] = t0;
+      }
+    }
+    in0 += (n_in[s] + 3) & ~(int64_t)3;                   // every segment starts 16-byte aligned
+    out0 += (n_out + 3) & ~(int64_t)3;
+  }
+  return (int)(nt > 0x7fffffff ? DVAE_EINVAL : nt);
+}
+
+DVAE_API int dvae_resample_lds_floats(int64_t P, int64_t Q, int taps) {
+  if (P < 1 || Q < 1 || taps < 1) return DVAE_EINVAL;
+  const int64_t span = ((int64_t)(RS_TILE - 1) * Q + P - 1) / P + 1 + taps + 4;
+  const int64_t cap = (span + 3) & ~(int64_t)3;
+  return cap * 4 > 64 * 1024 ? DVAE_EINVAL : (int)cap;
+}
+
+DVAE_API int dvae_resample_batch(const float* x, float* y, const int64_t* segs, const int64_t* filters, const float* weights,
+                                 const int64_t* tiles, int ntiles, int lds_floats, void* stream) {
+  if (!x || !y || !segs || !filters || !weights || !tiles || ntiles < 1 || lds_floats < 4 || (lds_floats & 3) ||
+      lds_floats * 4 > 64 * 1024 || ((((uintptr_t)x) | ((uintptr_t)y)) & 15))
+    return DVAE_EINVAL;
+  hipLaunchKernelGGL(resample_kernel, dim3((unsigned)ntiles), dim3(RS_TILE), (size_t)lds_floats * 4, (hipStream_t)stream,
+                     x, y, segs, filters, weights, tiles, lds_floats);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_volume_normalize(float* y, const int64_t* segs, int nseg, const int64_t* tiles, int ntiles,
+                                   const int64_t* tile_first, double* part, double target_dbfs, int increase_only,
+                                   double* ms_out, float* gain, int* silent, void* stream) {
+  if (!y || !segs || !tiles || !tile_first || !part || !gain || !silent || nseg < 1 || ntiles < 1 ||
+      !(target_dbfs < 1e3 && target_dbfs > -1e3))
+    return DVAE_EINVAL;
+  hipLaunchKernelGGL(sumsq_tiles_kernel, dim3((unsigned)ntiles), dim3(NV_THREADS), 0, (hipStream_t)stream, y, segs, tiles,
+                     part);
+  int rc = dvae_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(volume_finalize_kernel, dim3((unsigned)((nseg + 127) / 128)), dim3(128), 0, (hipStream_t)stream,
+                     segs, nseg, tile_first, part, target_dbfs, increase_only, ms_out, gain, silent);
+  rc = dvae_check_launch();
+  if (rc) return rc;
+  hipLaunchKernelGGL(volume_scale_kernel, dim3((unsigned)ntiles), dim3(NV_THREADS), 0, (hipStream_t)stream, y, segs, tiles,
+                     gain);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_stft_frames_seg(const float* wav, const int64_t* segs, int nseg, int64_t rows, const float* window,
+                                  float* frames, int fsize, int hop, int left, void* stream) {
+  if (!wav || !segs || !window || !frames || nseg < 1 || rows < 1 || fsize < 4 || (fsize & 3) || hop < 1 || left < 0 ||
+      (((uintptr_t)frames) & 15))
+    return DVAE_EINVAL;
+  const int64_t work = rows * (fsize >> 2);
+  hipLaunchKernelGGL(stft_frames_seg_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     wav, segs, nseg, rows, window, frames, fsize, hop, left);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_mel_db_normalize_seg(const float* mel, float* out, const int64_t* segs, int nseg, int64_t rows,
+                                       int n_mels, float min_level, float ref_level_db, float min_level_db, void* stream) {
+  if (!mel || !out || !segs || nseg < 1 || rows < 1 || rows > ((int64_t)1 << 36) || n_mels < 1 || !(min_level > 0.f) ||
+      !(min_level_db < 0.f))
+    return DVAE_EINVAL;
+  dim3 grid((unsigned)((rows + 31) / 32), (n_mels + 31) / 32);
+  hipLaunchKernelGGL(mel_db_normalize_seg_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel, out, segs, nseg, rows,
+                     n_mels, min_level, ref_level_db, min_level_db);
   return dvae_check_launch();
 }

@@ -97,13 +97,21 @@ class MelFrontend:
         extra = 1 if length % self.hop == 0 else 2
         return (length + 2 * pad - self.fsize) // self.hop + extra
 
-    def melspectrogram_batch(self, wavs: Sequence) -> list:
-        """List of 1-D waveforms (numpy / tensors, any length >= 1) -> list of device tensors [80, M_i]."""
+    def melspectrogram_batch(self, wavs: Sequence, unsplit: bool = False) -> list:
+        """List of 1-D waveforms (numpy / tensors, any length >= 1) -> list of device tensors [80, M_i].
+        unsplit=True: the pinned path of the corpus tool (preprocess.py): both contractions with ONE k-split and the
+        segmented framing / dB passes, so that an utterance's mel is bit-identical whatever batch it lands in (the default
+        lets the contraction pick a split from the row count)."""
         L = lib()
         sigs = [torch.as_tensor(np.asarray(w, dtype=np.float32) if not torch.is_tensor(w) else w)
                 .to(self.device, torch.float32).contiguous().view(-1) for w in wavs]
         if not sigs or any(s.numel() < 1 for s in sigs):
             raise ValueError("melspectrogram: empty waveform")
+        if unsplit:
+            from .preprocess import pack
+            wav, offs = pack(sigs, self.device)
+            out, ms = self._mel_packed(wav, offs, [s.numel() for s in sigs])
+            return self.unpack(out, ms)
         ms = [self.num_frames(s.numel()) for s in sigs]
         rows = sum(ms)
         frames = torch.empty((rows, self.fsize), device=self.device, dtype=torch.float32)
@@ -126,6 +134,50 @@ class MelFrontend:
             outs.append(out)
             r += m
         return outs
+
+    def _gemm(self, A, B, C, K):
+        # C[rows, N] = A[rows, K] B[N, K]^T, fp32 products, ONE k-split whatever the row count (MelInverter._gemm)
+        ops.gemm(A, B, C, None, A.shape[0], B.shape[0], K, K, K, B.shape[0], True, True, ops.ACT_NONE, ops.EPI_STORE, 1,
+                 self.mode)
+
+    def _mel_packed(self, wav, sample0, lengths):
+        """Pinned mel of the signals wav[sample0[i], sample0[i] + lengths[i]) of one device buffer: five launches for the
+        whole batch -> (packed out: the [80, M_i] blocks back to back, [M_i])"""
+        L = lib()
+        ns = [int(n) for n in lengths]
+        if not ns or min(ns) < 1:
+            raise ValueError("melspectrogram: empty waveform")
+        ms = [self.num_frames(n) for n in ns]
+        table = np.zeros((len(ns), 4), dtype=np.int64)          # {row0, M, sample0, n}: dvae_gl_segment_table's layout
+        table[:, 0] = np.concatenate([[0], np.cumsum(ms)[:-1]])
+        table[:, 1] = ms
+        table[:, 2] = np.asarray(sample0, dtype=np.int64)
+        table[:, 3] = ns
+        segs = torch.from_numpy(table).to(self.device)
+        rows = int(sum(ms))
+        frames = torch.empty((rows, self.fsize), device=self.device, dtype=torch.float32)
+        check(L.dvae_stft_frames_seg(ptr(wav), ptr(segs), len(ns), rows, ptr(self.window), ptr(frames), self.fsize,
+                                     self.hop, self.fsize - self.hop, stream()), "dvae_stft_frames_seg")
+        reim = torch.empty((rows, 2 * self.nbp), device=self.device, dtype=torch.float32)
+        self._gemm(frames, self.dft_basis, reim, self.fsize)
+        del frames
+        mag = torch.empty((rows, self.nbp), device=self.device, dtype=torch.float32)
+        check(L.dvae_stft_magnitude(ptr(reim), ptr(mag), rows, self.nbp, stream()), "dvae_stft_magnitude")
+        del reim
+        mel = torch.empty((rows, self.n_mels), device=self.device, dtype=torch.float32)
+        self._gemm(mag, self.mel_basis, mel, self.nbp)
+        out = torch.empty(rows * self.n_mels, device=self.device, dtype=torch.float32)
+        check(L.dvae_mel_db_normalize_seg(ptr(mel), ptr(out), ptr(segs), len(ns), rows, self.n_mels, self.min_level,
+                                          self.ref_level_db, self.min_level_db, stream()), "dvae_mel_db_normalize_seg")
+        return out, ms
+
+    def unpack(self, out, ms):
+        """packed [80, M_i] blocks (a device or host tensor / array) -> list of [80, M_i] views"""
+        res, r = [], 0
+        for m in ms:
+            res.append(out[self.n_mels * r:self.n_mels * (r + m)].reshape(self.n_mels, m))
+            r += m
+        return res
 
     def melspectrogram(self, wav):
         """One waveform -> [80, M] in [0, 1] (utils.py:68-73)."""

@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 308
+#define DVAE_ABI_VERSION 309
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -478,6 +478,46 @@ int dvae_gl_phase(const float* rebuilt, const float* prev, const float* mag, flo
 int dvae_gl_segment_table(const int* frames, int nseg, int fsize, int hop, int64_t* table);
 int dvae_ola_gather(const float* y, const int64_t* segs, int nseg, int64_t rows, const float* window, float* out,
                     int64_t out_len, int fsize, int hop, int mode, int norm, void* stream);
+
+/* ---- corpus preprocessing (python -m dvae_amd.preprocess): preprocessing/encoder/audio.py:22-51 `preprocess_wav` on a
+ * packed batch of utterances of any source rates and lengths, one launch per pass for the whole batch.  The bits of an
+ * output depend only on its own utterance and rate (not on the batch, not on the run): fixed tap / summation orders, one
+ * writer per element, no atomics.
+ * dvae_resample_segment_table (host): segment s of n_in[s] samples at filter filt[s] (filters[nfilt][6] = {P, Q, taps,
+ *   base, woff, 0}: ratio sr_new / sr_old = P / Q in lowest terms, `taps` weights per phase at woff + phase * taps,
+ *   tap c of output t reads input floor(t Q / P) - base + c) -> table[nseg][6] = {in0, n_in, out0, n_out, n_valid, filt}
+ *   with n_valid = floor(n_in P / Q) (resampy's int(n * ratio)), n_out = ceil(n_in P / Q) (librosa.resample fix=True),
+ *   in0 / out0 packed offsets rounded up to multiples of 4; tiles[ntiles][2] = {segment, t0} every `tile` outputs
+ *   (tiles NULL: count only).  Returns ntiles, DVAE_EINVAL on a bad filter id, n_valid < 1 (resampy raises) or
+ *   more than max_tiles tiles.
+ * dvae_resample_lds_floats (host): the LDS floats a DVAE_RESAMPLE_TILE-output tile of filter (P, Q, taps) stages;
+ *   DVAE_EINVAL above 64 KB.  dvae_resample_batch takes the maximum over the batch's filters.
+ * dvae_resample_batch: resampy.resample(x, sr_old, sr_new, filter="kaiser_best") (resampy/interp.py resample_f) per
+ *   segment, with the float64 per-phase weights rounded to fp32 (frontend.resample_filter): y[out0 + t] = sum_c w * x
+ *   in tap order, inputs outside [0, n_in) zero (the tap bounds of resampy), y = 0 for n_valid <= t < n_out.  tiles
+ *   from dvae_resample_segment_table with tile = DVAE_RESAMPLE_TILE; x, y 16-byte aligned.
+ * dvae_volume_normalize: audio.py:121-127 normalize_volume(y, target_dbfs, increase_only) on every segment of the
+ *   resampled batch, in place: float64 sum of squares per DVAE_VOLUME_TILE-sample tile (part[ntiles]), per segment
+ *   ms = sum over its tiles tile_first[s] .. tile_first[s+1] in order / n_out, gain = 10^((target - 10 log10 ms) / 20)
+ *   (1 where increase_only and the change is < 0), y *= gain.  ms == 0: silent[s] = 1, gain 1 (the reference would
+ *   write 0 * inf = NaN).  tiles from dvae_resample_segment_table with tile = DVAE_VOLUME_TILE; ms_out optional.
+ * dvae_stft_frames_seg / dvae_mel_db_normalize_seg: dvae_stft_frames / dvae_mel_db_normalize on a packed batch, bit for
+ *   bit, with the dvae_gl_segment_table layout {row0, M, sample0, n} in device memory: frame rows of segment s are
+ *   [row0, row0 + M) of signal wav[sample0, sample0 + n); its [n_mels, M] block of `out` starts at n_mels * row0. */
+#define DVAE_RESAMPLE_TILE 256
+#define DVAE_VOLUME_TILE 2048
+int dvae_resample_segment_table(const int64_t* n_in, const int* filt, int nseg, const int64_t* filters, int nfilt,
+                                int tile, int64_t* table, int64_t* tiles, int64_t max_tiles);
+int dvae_resample_lds_floats(int64_t P, int64_t Q, int taps);
+int dvae_resample_batch(const float* x, float* y, const int64_t* segs, const int64_t* filters, const float* weights,
+                        const int64_t* tiles, int ntiles, int lds_floats, void* stream);
+int dvae_volume_normalize(float* y, const int64_t* segs, int nseg, const int64_t* tiles, int ntiles,
+                          const int64_t* tile_first, double* part, double target_dbfs, int increase_only, double* ms_out,
+                          float* gain, int* silent, void* stream);
+int dvae_stft_frames_seg(const float* wav, const int64_t* segs, int nseg, int64_t rows, const float* window,
+                         float* frames, int fsize, int hop, int left, void* stream);
+int dvae_mel_db_normalize_seg(const float* mel, float* out, const int64_t* segs, int nseg, int64_t rows, int n_mels,
+                              float min_level, float ref_level_db, float min_level_db, void* stream);
 
 /* ---- opt-in per-family kernel timing with HIP events on the launch stream (bench.py roofline) ----
  * family: 0 = off, 1 = GEMM/conv contraction kernel, 2 = LSTM step kernels.
