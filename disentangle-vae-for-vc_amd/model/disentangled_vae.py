@@ -31,7 +31,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..ops import (ACT_NONE, fanout, ACT_RELU, ACT_TANH, ConvBnActFn, FramesToMelFn, LatentFn, LinearFn, LstmLayerFn,
-                   LstmStack2Fn, Permute102Fn, mel_to_frames)
+                   LstmStack2Fn, Permute102Fn, mel_frames, mel_to_frames)
 from ..derived import DerivedWeights
 from ..optim import FlatAdam
 from .variational_base_vae import VariationalBaseModelVAE
@@ -181,13 +181,13 @@ class Postnet(nn.Module):
     def forward(self, x):
         """x [B, 80, T] -> [B, 80, T], as called by voice conversion (variational_base_vae.py:292)."""
         B, C, T = x.shape
-        y = self.forward_frames(mel_to_frames(x.contiguous()), B, 1)
+        y = self.forward_frames(mel_frames(x), B, 1)
         return FramesToMelFn.apply(y, B, C, T)
 
     def forward_plus_input(self, x):
         """x + postnet(x) with the residual fused into the last BatchNorm apply (variational_base_vae.py:292-293)."""
         B, C, T = x.shape
-        xf = mel_to_frames(x.contiguous())
+        xf = mel_frames(x)
         return FramesToMelFn.apply(self.forward_frames(xf, B, 1, residual=xf), B, C, T)
 
 
@@ -368,7 +368,7 @@ class DisentangledVAE(nn.Module):
         self._check(x)
         self._refresh_derived()
         B, _, T = x.shape
-        style, content = self._encode_frames(mel_to_frames(x.contiguous()), T, B, 1)
+        style, content = self._encode_frames(mel_frames(x), T, B, 1)
         s, c = self.speaker_size, self.latent_dim - self.speaker_size
         return style[:, :s], style[:, s:], content[:, :c], content[:, c:]
 
@@ -377,7 +377,7 @@ class DisentangledVAE(nn.Module):
         self._check(x)
         self._refresh_derived()
         B, _, T = x.shape
-        return self._encode_frames(mel_to_frames(x.contiguous()), T, B, 1)
+        return self._encode_frames(mel_frames(x), T, B, 1)
 
     def _reparameterize(self, mu, logvar, train=True):
         """API-compatible standalone form (disentangled_vae.py:222-228).  The training path does not call it:

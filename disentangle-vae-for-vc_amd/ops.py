@@ -30,7 +30,7 @@ grad_ready_hook: Optional[Callable[[torch.Tensor], None]] = None
 USE_SIDE_STREAM = os.environ.get("DVAE_SIDE_STREAM", "0") != "0"   # measured gain 1.5 %: off by default
 _side_stream = None
 _side_dirty = False
-_cb_queued = False
+_cb_task = None              # graph task id of the backward pass whose final callback is queued (None: no such pass)
 
 
 _fold_owners: list = []      # optimisers with k-split slabs pending from the running backward pass (see _defer_fold)
@@ -38,8 +38,8 @@ _fold_owners: list = []      # optimisers with k-split slabs pending from the ru
 
 def _end_of_backward():
     # autograd final callback: runs on the thread that called backward(), after the last node
-    global _cb_queued
-    _cb_queued = False
+    global _cb_task
+    _cb_task = None
     join_side()
     # the k-split slabs of this pass's weight gradients: ONE table-driven launch, so that `.grad` is complete when backward()
     # returns (a reducer that issued from its hooks has summed its own already)
@@ -48,15 +48,17 @@ def _end_of_backward():
 
 
 def _queue_end_of_backward() -> bool:
-    """True when the final callback is (now) queued on the running backward pass; False outside one"""
-    global _cb_queued
-    if _cb_queued:
+    """True when the final callback is (now) queued on the running backward pass; False outside one.  The flag names the
+    pass it was queued on: a pass that raised skips its final callbacks, and a later pass must still queue its own."""
+    global _cb_task
+    task = torch._C._current_graph_task_id()
+    if task >= 0 and _cb_task == task:
         return True
     try:
         torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
-        _cb_queued = True
     except RuntimeError:
         return False
+    _cb_task = task
     return True
 
 
@@ -76,16 +78,12 @@ class side_work:
         self.ctx = None
 
     def __enter__(self):
-        global _side_dirty, _cb_queued
+        global _side_dirty
         if not USE_SIDE_STREAM:
             return self
-        if not _cb_queued:
-            # gradients must be visible to the caller's stream when backward() returns
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(_end_of_backward)
-                _cb_queued = True
-            except RuntimeError:
-                pass   # not inside a backward pass: the caller joins explicitly (join_side)
+        # gradients must be visible to the caller's stream when backward() returns (outside a backward pass the caller
+        # joins explicitly: join_side)
+        _queue_end_of_backward()
         side = side_stream()
         side.wait_stream(torch.cuda.current_stream())
         self.ctx = torch.cuda.stream(side)
@@ -231,8 +229,28 @@ def _fold_launch(entries):
         check(lib().dvae_slab_fold(arr, len(entries), stream()), "dvae_slab_fold")
 
 
+def _claim_slabs(buf: torch.Tensor, owners):
+    """A launch is about to write the slab buffer `buf` of an optimiser-owned gradient: first add every slab set of `owners`
+    still pending in its range to its gradient.  A parameter used twice in one backward pass would otherwise have its first
+    use's splits overwritten by the second launch before they were summed.  Matched by address range, not by key: one buffer
+    is pending under two gradients (the persistent LSTM's bias slabs: bias_ih and bias_hh), and a batched launch's buffer
+    holds several parameters' slabs at offsets.  Nothing pending in range (every parameter used once): no launch."""
+    lo = buf.data_ptr()
+    hi = lo + 4 * buf.numel()
+    seen = []
+    for ow in owners:
+        pend = getattr(ow, "_slab_pending", None) if ow is not None else None
+        if not pend or any(ow is o for o in seen):
+            continue
+        seen.append(ow)
+        ks = [k for k, e in pend.items() if e.slab < hi and lo < e.slab + 4 * e.slab_stride * e.nslab]
+        if ks:
+            _fold_launch([pend.pop(k) for k in ks])
+
+
 def _defer_fold(grad: torch.Tensor, owner, slab_ptr: int, stride: int, nslab: int, n: int = None):
-    """`nslab` slabs are to be added to `grad` (n elements, a multiple of 4): later when an optimiser owns it, now otherwise"""
+    """`nslab` slabs are to be added to `grad` (n elements, a multiple of 4): later when an optimiser owns it, now otherwise.
+    The launch that wrote them claimed their buffer first (_claim_slabs)."""
     if nslab < 1:
         return
     n = _pad4(grad.numel()) if n is None else n
@@ -245,8 +263,9 @@ def _defer_fold(grad: torch.Tensor, owner, slab_ptr: int, stride: int, nslab: in
         return
     pend = owner.__dict__.setdefault("_slab_pending", {})
     key = (grad.data_ptr(), slab_ptr)
-    if key in pend:            # a second contribution to this gradient before the first was summed: sum that one now
-        _fold_launch([pend.pop(key)])
+    if key in pend:
+        raise RuntimeError("k-split slabs were overwritten before they were summed: the launch that wrote them did not "
+                           "claim its slab buffer (ops._claim_slabs)")
     pend[key] = e
     if not any(o is owner for o in _fold_owners):
         _fold_owners.append(owner)
@@ -291,6 +310,8 @@ def wgrad_gemm_batched(As, Bs, params, M, N, K, lda, ldb, split_k, mode, flags=0
             slab = _slab_store(owner)[key] = torch.empty(cap * stride, device=grads[0].device, dtype=torch.float32)
         else:
             slab, _ = _scratch_slabs(grads[0].device, cap * stride, 1)
+    if owner is not None:
+        _claim_slabs(slab, [_owner_of(p) for p in params])
     n = lib().dvae_gemm_f32_batched_slabs(arr(As), arr(Bs), arr(grads), nb, ptr(slab), stride, cap, M, N, K, lda, ldb, N, 0, 0,
                                           EPI_ACCUM, split_k, m, stream())
     if n < 1:
@@ -340,7 +361,11 @@ def wgrad_gemm(A, B, grad, owner, M, N, K, lda, ldb, a_kc, b_kc, split_k, mode, 
         gemm(A, B, grad, None, M, N, K, lda, ldb, N, a_kc, b_kc, ACT_NONE, EPI_ACCUM, 1, mode, flags)
         return
     cap = _cap_for(split_k)
-    slab, stride = _param_slabs(grad, cap, owner) if owner is not None else _scratch_slabs(grad.device, grad.numel(), cap)
+    if owner is not None:
+        slab, stride = _param_slabs(grad, cap, owner)
+        _claim_slabs(slab, (owner,))
+    else:
+        slab, stride = _scratch_slabs(grad.device, grad.numel(), cap)
     n = gemm_slabs(A, B, grad, None, M, N, K, lda, ldb, N, a_kc, b_kc, EPI_ACCUM, split_k, mode, slab, stride, cap, flags)
     if n > 1:
         _defer_fold(grad, owner, slab.data_ptr(), stride, n)
@@ -544,6 +569,29 @@ def mel_to_frames(x1, x2=None, dtype=torch.float32):
     return X
 
 
+class MelToFramesFn(torch.autograd.Function):
+    """[N, C, T] -> frame-major [T*N, C] (mel_to_frames) for an input that needs a gradient: the postnet applied to a decoder
+    output (disentangled_vae.py:273-274), encode() of a differentiable input.  Backward is the inverse layout change."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.dims = tuple(x.shape)
+        return mel_to_frames(x.contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        N, Cc, T = ctx.dims
+        dy = dy.contiguous()
+        dx = torch.empty((N, Cc, T), device=dy.device, dtype=torch.float32)
+        check(lib().dvae_frames_to_mel(ptr(dy), ptr(dx), N, Cc, T, stream()), "dvae_frames_to_mel")
+        return dx
+
+
+def mel_frames(x):
+    """mel_to_frames of one [N, C, T] tensor that passes the gradient on to x when x needs one"""
+    return MelToFramesFn.apply(x) if (x.requires_grad and torch.is_grad_enabled()) else mel_to_frames(x.contiguous())
+
+
 def transpose2d(x):
     R, Cc = x.shape
     out = torch.empty((Cc, R), device=x.device, dtype=torch.float32)
@@ -729,8 +777,11 @@ class ConvBnActFn(torch.autograd.Function):
             gw, own = _grad_buf(conv_wp), _owner_of(conv_wp)
             slab, stride = (None, 0)
             cap = _cap_for(sk)
-            if sk > 1:
-                slab, stride = _param_slabs(gw, cap, own) if own is not None else _scratch_slabs(dev, gw.numel(), cap)
+            if sk > 1 and own is not None:
+                slab, stride = _param_slabs(gw, cap, own)
+                _claim_slabs(slab, (own,))
+            elif sk > 1:
+                slab, stride = _scratch_slabs(dev, gw.numel(), cap)
             n = L.dvae_conv5_wgrad_slabs(ptr(dy), ptr(xa), ptr(gw), ptr(slab), stride, cap if sk > 1 else 0, R, n_seg,
                                          Cin, Cout, EPI_ACCUM, sk, _mflags(mode, dy, xa), stream())
             if n < 1:
@@ -852,6 +903,27 @@ def _lstm_derived(derived, params, mode):
     if len(params) == 2 and params[0][1].shape[1] == 64:
         return lstm_local_pair(params, int(mode))
     return [lstm_local(wi, wh, bi, bh, int(mode)) for (wi, wh, bi, bh) in params]
+
+
+def pers_bias_slabs(bi, bh, H: int) -> torch.Tensor:
+    """The [PERS_BIAS_SLABS][4H] buffer a persistent backward launch stores the bias gradient of (bi, bh) into: every row
+    group STORES its share into its own slab (no atomics); pers_bias_fold adds them to both bias gradients (nn.LSTM keeps
+    two) with the other k-split slabs, in a fixed order.  Claimed: slabs of an earlier use still pending are summed first."""
+    gbi = _grad_buf(bi)
+    _grad_buf(bh)
+    key = (gbi.data_ptr(), 4 * H, "pers_bias")
+    store = _slab_store(_owner_of(bi))
+    part = store.get(key)
+    if part is None:
+        part = store[key] = torch.zeros(_lib.PERS_BIAS_SLABS * 4 * H, device=gbi.device, dtype=torch.float32)
+    _claim_slabs(part, (_owner_of(bi), _owner_of(bh)))
+    return part
+
+
+def pers_bias_fold(bi, bh, part: torch.Tensor, H: int):
+    """The slabs of `part` (pers_bias_slabs), written by the launch, are to be added to both bias gradients."""
+    for par in (bi, bh):
+        _defer_fold(par.grad, _owner_of(par), part.data_ptr(), 4 * H, _lib.PERS_BIAS_SLABS, n=4 * H)
 
 
 class LstmLayerFn(torch.autograd.Function):
@@ -979,21 +1051,12 @@ class LstmLayerFn(torch.autograd.Function):
         if pers:
             _pers_fill(dirs[0], dev)
         if pers_bias:
-            # the persistent launch also leaves the bias gradients (column sums of dG): no colsum pass below.  Every row
-            # group STORES its share into its own slab (no atomics); the slabs are added to both bias gradients (nn.LSTM
-            # keeps two) with the other k-split slabs, in a fixed order
-            bi, bh = params[0][2], params[0][3]
-            gbi, gbh = _grad_buf(bi), _grad_buf(bh)
-            key = (gbi.data_ptr(), 4 * H, "pers_bias")
-            store = _slab_store(_owner_of(bi))
-            part = store.get(key)
-            if part is None:
-                part = store[key] = torch.zeros(_lib.PERS_BIAS_SLABS * 4 * H, device=dev, dtype=torch.float32)
+            # the persistent launch also leaves the bias gradients (column sums of dG): no colsum pass below
+            part = pers_bias_slabs(params[0][2], params[0][3], H)
             dirs[0].dbias_part = ptr(part)
         check(L.dvae_lstm_seq_bwd(dirs, ndir, T, N, H, ldh, st), "dvae_lstm_seq_bwd")
         if pers_bias:
-            for gb, par in ((gbi, bi), (gbh, bh)):
-                _defer_fold(gb, _owner_of(par), part.data_ptr(), 4 * H, _lib.PERS_BIAS_SLABS, n=4 * H)
+            pers_bias_fold(params[0][2], params[0][3], part, H)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((R, In), device=dev, dtype=torch.float32)

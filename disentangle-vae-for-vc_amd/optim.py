@@ -112,6 +112,9 @@ class FlatAdam:
             if getattr(p, "_dvae_grad_store_first", False):
                 p._dvae_sf_writes = 0
         self.__dict__.get("_slab_pending", {}).clear()      # slabs of an abandoned backward pass are not this step's
+        from . import ops
+        if any(o is self for o in ops._fold_owners):        # ... nor is the fold a backward pass that raised never ran
+            ops._fold_owners[:] = [o for o in ops._fold_owners if o is not self]
         if self._clean:
             return      # the previous step's Adam launch cleared these ranges and nothing has accumulated since
         for lo, hi in self._zero_ranges:

@@ -468,3 +468,144 @@ def test_trajectory_band_is_monotone_and_floored(golden_dir):
     # what the fixture says about the reference itself: agrees with itself at step 1, is chaotic by step 5
     spread = np.abs(g["traj_fp32"] - g["traj_fp32"][-1][None]).max(0) / np.abs(g["traj_fp32"][-1])
     assert spread[0].max() < 1e-6 and spread[4].max() > 1e-2
+
+
+class _SlabTraffic:
+    """The k-split slab traffic of dvae_amd.ops with every launch replaced (no device work): each contraction "launches"
+    n = 4 splits into its slab buffer, every fold is recorded.  Checks, as the events come, that no launch writes slabs that
+    are still waiting to be summed, and that every slab set is summed exactly once."""
+
+    N = 4
+
+    def __init__(self, ops):
+        self.ops = ops
+        self.live = {}          # (gradient address, slab address) -> [lo, hi) of slabs written and not summed yet
+        self.writes = 0
+        self.folded = 0
+        self.errors = []
+
+    def write(self, cs, lo, nslab, stride):
+        """one launch stores `nslab` slabs at `lo`, to be summed into each gradient of `cs`"""
+        hi = lo + 4 * nslab * stride
+        for (gc, glo), (a, b) in self.live.items():
+            if a < hi and lo < b:
+                self.errors.append(f"slabs of gradient {gc:#x} at {glo:#x} overwritten before they were summed")
+        for c in cs:
+            self.live[(c, lo)] = (lo, hi)
+        self.writes += 1
+
+    def fold(self, entries):
+        for e in entries:
+            if self.live.pop((e.c, e.slab), None) is None:
+                self.errors.append(f"slabs at {e.slab:#x} summed into {e.c:#x} but not (or no longer) written")
+            self.folded += 1
+
+    # the replaced launches
+    def gemm_slabs(self, A, B, Cout, bias, M, N, K, lda, ldb, ldc, a_kc, b_kc, epi, split_k, mode, slab, stride, cap,
+                   flags=0):
+        assert self.N <= cap
+        self.write([Cout.data_ptr()], slab.data_ptr(), self.N, stride)
+        return self.N
+
+    def dvae_gemm_f32_batched_slabs(self, As, Bs, Cs, nb, slab, stride, cap, *rest):
+        assert self.N * nb <= cap
+        for b in range(nb):
+            self.write([Cs[b]], slab + 4 * b * self.N * stride, self.N, stride)
+        return self.N
+
+
+def _reuse_harness(monkeypatch):
+    """(ops, traffic, optimiser, params, ReuseFn): ReuseFn.apply(x, kind) is the identity forward whose backward drives one
+    owned weight gradient through ops' k-split path — kind "gemm" (wgrad_gemm), "batched" (wgrad_gemm_batched, two
+    parameters in one launch) or "bias" (the persistent LSTM's bias slabs, pending under bias_ih and bias_hh)."""
+    import dvae_amd  # noqa: F401
+    from dvae_amd import ops
+    from dvae_amd.optim import FlatAdam
+    tr = _SlabTraffic(ops)
+    monkeypatch.setattr(ops, "gemm_slabs", tr.gemm_slabs)
+    monkeypatch.setattr(ops, "lib", lambda: tr)
+    monkeypatch.setattr(ops, "stream", lambda: 0)
+    monkeypatch.setattr(ops, "_fold_launch", lambda entries: tr.fold(entries) if entries else None)
+    monkeypatch.setattr(ops, "_cb_task", None)                # no final callback queued by an earlier test's pass
+    monkeypatch.setattr(ops, "_fold_owners", [])
+    H = 4
+    ps = {n: torch.nn.Parameter(torch.randn(*s)) for n, s in
+          (("w", (8, 12)), ("w1", (16, 8)), ("w2", (16, 8)), ("bi", (4 * H,)), ("bh", (4 * H,)))}
+    opt = FlatAdam(list(ps.items()), lr=1e-3)
+
+    class ReuseFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, kind):
+            ctx.kind = kind
+            return x.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            if ctx.kind == "gemm":
+                w = ps["w"]
+                ops.wgrad_gemm(0, 0, ops._grad_buf(w), ops._owner_of(w), 8, 12, 1024, 8, 12, False, False, 4, ops.MODE_F32)
+            elif ctx.kind == "batched":
+                ops.wgrad_gemm_batched([0, 0], [0, 0], [ps["w1"], ps["w2"]], 16, 8, 1024, 16, 8, 4, ops.MODE_F32)
+            else:
+                part = ops.pers_bias_slabs(ps["bi"], ps["bh"], H)
+                # the persistent launch: one slab set, summed into both bias gradients
+                tr.write([ps["bi"].grad.data_ptr(), ps["bh"].grad.data_ptr()], part.data_ptr(), ops._lib.PERS_BIAS_SLABS,
+                         4 * H)
+                ops.pers_bias_fold(ps["bi"], ps["bh"], part, H)
+            return g, None
+
+    return ops, tr, opt, ps, ReuseFn
+
+
+@pytest.mark.parametrize("kind", ["gemm", "batched", "bias"])
+@pytest.mark.parametrize("uses", [1, 2, 3])
+def test_reused_owned_gradient_folds_each_launch_once_before_its_slabs_are_rewritten(monkeypatch, kind, uses):
+    """An optimiser-owned weight used `uses` times in ONE backward pass (encode(x1) and encode(x2), shared modules): each use's
+    launch stores its k-splits into the parameter's one slab buffer, so the slabs of the previous use must be summed BEFORE
+    the next launch writes it (ops._claim_slabs).  Summing them only afterwards lost the first use's splits and counted the
+    last one twice.  Every slab set is summed exactly once, and none is left pending when backward() returns."""
+    ops, tr, opt, ps, ReuseFn = _reuse_harness(monkeypatch)
+    x = torch.randn(3, requires_grad=True)
+    y = x
+    for _ in range(uses):
+        y = ReuseFn.apply(y, kind)
+    y.sum().backward()
+    assert not tr.errors, tr.errors
+    assert tr.writes == uses * (2 if kind == "batched" else 1)
+    assert tr.folded == uses * (1 if kind == "gemm" else 2) and not tr.live    # batched: two parameters, bias: two gradients
+    assert not opt.__dict__.get("_slab_pending") and not ops._fold_owners and ops._cb_task is None
+
+
+@pytest.mark.parametrize("zero_grad", [False, True])
+def test_backward_that_raised_leaves_no_stale_end_of_backward_state(monkeypatch, zero_grad):
+    """A backward pass that raises skips autograd's final callbacks.  The next pass must still queue its own (the flag names
+    the graph task it was queued on), so `.grad` is complete when that backward() returns — not only after
+    FlatAdam.step.  With or without optimizer.zero_grad() in between."""
+    ops, tr, opt, ps, ReuseFn = _reuse_harness(monkeypatch)
+
+    class Boom(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            return x.clone()
+
+        @staticmethod
+        def backward(ctx, g):
+            raise RuntimeError("host-side failure inside backward")
+
+    x = torch.randn(3, requires_grad=True)
+    y = ReuseFn.apply(ReuseFn.apply(Boom.apply(x), "gemm"), "bias")       # backward: bias, gemm, then Boom raises
+    with pytest.raises(RuntimeError, match="host-side failure"):
+        y.sum().backward()
+    assert opt.__dict__.get("_slab_pending")                  # what the aborted pass left: its callback never ran
+    if zero_grad:
+        opt.zero_grad()
+        assert not opt.__dict__.get("_slab_pending") and not ops._fold_owners
+        tr.live.clear()                                       # discarded with the aborted step's gradients
+    for kinds in (("gemm", "bias"), ("batched",)):            # two clean passes: the second finds nothing stale either
+        y = x
+        for k in kinds:
+            y = ReuseFn.apply(y, k)
+        y.sum().backward()
+        assert not tr.errors, tr.errors
+        assert not opt.__dict__.get("_slab_pending"), "slabs still pending when backward() returned"
+        assert not tr.live and not ops._fold_owners and ops._cb_task is None
