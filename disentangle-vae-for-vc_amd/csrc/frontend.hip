@@ -443,6 +443,215 @@ __global__ void mel_db_normalize_seg_kernel(const float* __restrict__ mel, float
   }
 }
 
+
+// ---- mel-cepstral distortion (evaluate.py; preprocessing/MCD_calculate.py:54-103): the passes around the three
+// contractions of the feature pass (frames x DFT basis, logP x sp2mc matrix, P x lag basis) and the batched exact DTW.
+// No atomics, one writer per output element, fixed orders: a pair's bits do not depend on the batch or the run.
+
+// reim[row][0..nbp) = Re, [nbp..2nbp) = Im  ->  P = Re^2 + Im^2, logP = ln(max(P, floor)); bins j >= nb are 0 in both.
+// One thread per 4 consecutive bins (16-byte loads and stores; nbp is a multiple of 4).
+__global__ void log_power_kernel(const float* __restrict__ reim, float* __restrict__ pw, float* __restrict__ lp,
+                                 int64_t rows, int nb, int nbp, float floor_) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int per_row = nbp >> 2;
+  if (idx >= rows * per_row) return;
+  const int64_t r = idx / per_row;
+  const int j = ((int)(idx - r * per_row)) << 2;
+  const f32x4 re = *reinterpret_cast<const f32x4*>(reim + r * 2 * nbp + j);
+  const f32x4 im = *reinterpret_cast<const f32x4*>(reim + r * 2 * nbp + nbp + j);
+  f32x4 p, l;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const bool in = j + e < nb;
+    p[e] = in ? fmaf(re[e], re[e], im[e] * im[e]) : 0.f;
+    l[e] = in ? logf(fmaxf(p[e], floor_)) : 0.f;
+  }
+  *reinterpret_cast<f32x4*>(pw + r * nbp + j) = p;
+  *reinterpret_cast<f32x4*>(lp + r * nbp + j) = l;
+}
+
+// One workgroup per utterance {row0, M, ..}.  r[row][0] = r(0), r[row][1..nlag] = r(lag) (the lag-basis contraction),
+// gain[1..nlag] = r_w(0) / r_w(lag).  peak = max_lag(r * gain) / r(0) (0 where r(0) = 0); voiced = r(0) > 0 and
+// r(0) >= rel_min * max r(0) over the utterance and peak >= peak_min.  Then the voiced frames' first MCD_DIM coefficients of
+// mc[row][0..ldm) go to feats[row0 + k][MCD_DIM] in time order (k = the frame's rank among the voiced ones, from a fixed
+// 256-frame-chunk ballot scan), and count[utterance] = the number of voiced frames.
+constexpr int VC_THREADS = 256, VC_WAVES = VC_THREADS / 64, MCD_DIM = 24;
+__global__ void __launch_bounds__(VC_THREADS) voicing_compact_kernel(const float* __restrict__ r, int ldr, int nlag,
+                                                                    const float* __restrict__ gain,
+                                                                    const float* __restrict__ mc, int ldm,
+                                                                    const int64_t* __restrict__ segs, float peak_min,
+                                                                    float rel_min, float* __restrict__ peak,
+                                                                    int* __restrict__ voiced, float* __restrict__ feats,
+                                                                    int* __restrict__ count) {
+  __shared__ float red[VC_WAVES];
+  __shared__ float pk[VC_THREADS];
+  __shared__ int wsum[VC_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int64_t row0 = segs[4 * blockIdx.x], M = segs[4 * blockIdx.x + 1];
+  float m0 = 0.f;                                   // r(0) is a sum of non-negative terms
+  for (int64_t f = tid; f < M; f += VC_THREADS) m0 = fmaxf(m0, r[(row0 + f) * ldr]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m0 = fmaxf(m0, __shfl_xor(m0, o));
+  if (lane == 0) red[wid] = m0;
+  __syncthreads();
+  float mx = red[0];
+#pragma unroll
+  for (int w = 1; w < VC_WAVES; ++w) mx = fmaxf(mx, red[w]);
+  const float thr = rel_min * mx;
+  int base = 0;
+  for (int64_t c0 = 0; c0 < M; c0 += VC_THREADS) {
+    for (int q = 0; q < 64; ++q) {                  // wave wid: frames c0 + 64 wid + q, its lanes over the lags
+      const int64_t f = c0 + 64 * wid + q;
+      if (f >= M) break;
+      const float* rr = r + (row0 + f) * ldr;
+      float m = 0.f;
+      for (int t = 1 + lane; t <= nlag; t += 64) m = fmaxf(m, rr[t] * gain[t]);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+      if (lane == 0) pk[64 * wid + q] = m;
+    }
+    __syncthreads();
+    const int64_t f = c0 + tid;
+    int v = 0;
+    if (f < M) {
+      const float r0 = r[(row0 + f) * ldr];
+      const float p = r0 > 0.f ? pk[tid] / r0 : 0.f;
+      v = (r0 > 0.f && r0 >= thr && p >= peak_min) ? 1 : 0;
+      peak[row0 + f] = p;
+      voiced[row0 + f] = v;
+    }
+    const unsigned long long mask = __ballot(v);
+    const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[wid] = __popcll(mask);
+    __syncthreads();
+    int off = base, tot = 0;
+#pragma unroll
+    for (int w = 0; w < VC_WAVES; ++w) {
+      off += w < wid ? wsum[w] : 0;
+      tot += wsum[w];
+    }
+    if (v) {
+      const float* src = mc + (row0 + f) * ldm;
+      float* dst = feats + (row0 + off + rank) * MCD_DIM;
+#pragma unroll
+      for (int c = 0; c < MCD_DIM; c += 4)
+        *reinterpret_cast<f32x4*>(dst + c) = *reinterpret_cast<const f32x4*>(src + c);
+    }
+    base += tot;
+    __syncthreads();                                // pk / wsum are rewritten by the next chunk
+  }
+  if (tid == 0) count[blockIdx.x] = base;
+}
+
+// Exact DTW of one pair per workgroup, pair row {x_row0, nx, y_row0, ny} (int64) into the packed [., MCD_DIM] buffers.
+// D(i,j) = d(i,j) + min(D(i-1,j), D(i,j-1), D(i-1,j-1)) with d the float64 euclidean distance of the fp32 rows; a tie goes
+// to the first of the three in that order; the path length L rides along with D (L(0,0) = 1), so no traceback.
+// Anti-diagonal sweep along the shorter sequence A (index a; the longer is B, index b = diagonal - a): thread t owns
+// a = t + DTW_THREADS * s for slots s < ceil(na / DTW_THREADS).  Cell (a, b) reads (a-1, b) from the previous diagonal in
+// LDS (double-buffered, one barrier per diagonal), (a, b-1) from its own register and (a-1, b-1) from the register that
+// kept last diagonal's LDS read.  Feature rows come through L1 / L2 in 16-byte loads.
+constexpr int DTW_THREADS = 256, DTW_SLOTS = 16, DTW_MAX_SHORT = DTW_THREADS * DTW_SLOTS;
+static_assert(DTW_MAX_SHORT == 4096 && MCD_DIM == 24, "DVAE_DTW_MAX_SHORT / DVAE_MCD_DIM of include/dvae_hip.h");
+
+__device__ __forceinline__ double dist_row(const float* __restrict__ p, const float* __restrict__ q) {
+  double acc = 0.0;
+#pragma unroll
+  for (int c = 0; c < MCD_DIM; c += 4) {
+    const f32x4 u = *reinterpret_cast<const f32x4*>(p + c), v = *reinterpret_cast<const f32x4*>(q + c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double t = (double)u[e] - (double)v[e];
+      acc = fma(t, t, acc);
+    }
+  }
+  return sqrt(acc);
+}
+
+__global__ void __launch_bounds__(DTW_THREADS) dtw_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                          const int64_t* __restrict__ pairs, double* __restrict__ cost,
+                                                          int64_t* __restrict__ length) {
+  __shared__ double cs[2][DTW_MAX_SHORT];
+  __shared__ int ls[2][DTW_MAX_SHORT];
+  const int tid = threadIdx.x;
+  const int64_t* pr = pairs + 4 * blockIdx.x;
+  const int64_t nx = pr[1], ny = pr[3];
+  if (nx < 1 || ny < 1) {                           // a side without voiced frames: no score
+    if (tid == 0) {
+      cost[blockIdx.x] = __builtin_nan("");
+      length[blockIdx.x] = 0;
+    }
+    return;
+  }
+  const bool swap = nx > ny;                        // A = the shorter side; a = i unless swapped (then a = j)
+  const float* __restrict__ A = swap ? y + pr[2] * MCD_DIM : x + pr[0] * MCD_DIM;
+  const float* __restrict__ B = swap ? x + pr[0] * MCD_DIM : y + pr[2] * MCD_DIM;
+  const int na = (int)(swap ? ny : nx);
+  const int64_t nb = swap ? nx : ny;
+  const int S = (na + DTW_THREADS - 1) / DTW_THREADS;
+  const double inf = __builtin_inf();
+  double cl[DTW_SLOTS], cu[DTW_SLOTS];              // own cell of the previous diagonal; last diagonal's (a-1) read
+  int ll[DTW_SLOTS], lu[DTW_SLOTS];
+#pragma unroll
+  for (int s = 0; s < DTW_SLOTS; ++s) {
+    cl[s] = cu[s] = inf;
+    ll[s] = lu[s] = 0;
+  }
+  const int64_t ndiag = (int64_t)na + nb - 1;
+  for (int64_t dg = 0; dg < ndiag; ++dg) {
+    const int cur = (int)(dg & 1);
+#pragma unroll
+    for (int s = 0; s < DTW_SLOTS; ++s) {
+      const int a = tid + DTW_THREADS * s;
+      const int64_t b = dg - a;
+      if (s < S && a < na && b >= 0 && b < nb) {
+        const double d = dist_row(A + (int64_t)a * MCD_DIM, B + b * MCD_DIM);
+        double c = d;
+        int l = 1;
+        if (a > 0 || b > 0) {
+          double cup = inf, clf = b > 0 ? cl[s] : inf, cdg = (a > 0 && b > 0) ? cu[s] : inf;
+          int lup = 0;
+          if (a > 0) {
+            cup = cs[cur ^ 1][a - 1];
+            lup = ls[cur ^ 1][a - 1];
+          }
+          // order (i-1, j), (i, j-1), (i-1, j-1): (a-1, b), (a, b-1) when a = i; (a, b-1), (a-1, b) when a = j
+          double bc = swap ? clf : cup;
+          int bl = swap ? ll[s] : lup;
+          const double c2 = swap ? cup : clf;
+          const int l2 = swap ? lup : ll[s];
+          if (c2 < bc) {
+            bc = c2;
+            bl = l2;
+          }
+          if (cdg < bc) {
+            bc = cdg;
+            bl = lu[s];
+          }
+          c = d + bc;
+          l = bl + 1;
+          cu[s] = cup;
+          lu[s] = lup;
+        }
+        cs[cur][a] = c;
+        ls[cur][a] = l;
+        cl[s] = c;
+        ll[s] = l;
+      }
+    }
+    __syncthreads();
+  }
+  const int last = na - 1;                          // cell (na-1, nb-1): its owner's register
+  if (tid == last % DTW_THREADS) {
+#pragma unroll
+    for (int s = 0; s < DTW_SLOTS; ++s) {
+      if (s == last / DTW_THREADS) {
+        cost[blockIdx.x] = cl[s];
+        length[blockIdx.x] = ll[s];
+      }
+    }
+  }
+}
+
 }  // namespace
 
 DVAE_API int dvae_stft_frames(const float* wav, int64_t n, const float* window, float* frames, int M, int fsize,
@@ -628,5 +837,45 @@ DVAE_API int dvae_mel_db_normalize_seg(const float* mel, float* out, const int64
   dim3 grid((unsigned)((rows + 31) / 32), (n_mels + 31) / 32);
   hipLaunchKernelGGL(mel_db_normalize_seg_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel, out, segs, nseg, rows,
                      n_mels, min_level, ref_level_db, min_level_db);
+  return dvae_check_launch();
+}
+
+
+// ---- mel-cepstral distortion
+DVAE_API int dvae_log_power(const float* reim, float* power, float* log_power, int64_t rows, int nb, int nbp, float floor_,
+                            void* stream) {
+  if (!reim || !power || !log_power || rows < 1 || nb < 1 || nbp < nb || (nbp & 3) || !(floor_ > 0.f) ||
+      ((((uintptr_t)reim) | ((uintptr_t)power) | ((uintptr_t)log_power)) & 15))
+    return DVAE_EINVAL;
+  const int64_t work = rows * (nbp >> 2);
+  hipLaunchKernelGGL(log_power_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reim,
+                     power, log_power, rows, nb, nbp, floor_);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_voicing_compact(const float* r, int ldr, int nlag, const float* gain, const float* mc, int ldm,
+                                  const int64_t* segs, int nseg, float peak_min, float rel_power_min, float* peak,
+                                  int* voiced, float* feats, int* count, void* stream) {
+  if (!r || !gain || !mc || !segs || !peak || !voiced || !feats || !count || nseg < 1 || nlag < 1 || ldr < nlag + 1 ||
+      ldm < MCD_DIM || (ldm & 3) || !(peak_min >= 0.f) || !(rel_power_min >= 0.f) ||
+      ((((uintptr_t)mc) | ((uintptr_t)feats)) & 15))
+    return DVAE_EINVAL;
+  hipLaunchKernelGGL(voicing_compact_kernel, dim3((unsigned)nseg), dim3(VC_THREADS), 0, (hipStream_t)stream, r, ldr, nlag,
+                     gain, mc, ldm, segs, peak_min, rel_power_min, peak, voiced, feats, count);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_dtw_batch(const float* x, const float* y, const int64_t* pairs, const int64_t* pairs_host, int npairs,
+                            double* cost, int64_t* length, void* stream) {
+  if (!x || !y || !pairs || !pairs_host || !cost || !length || npairs < 1 || ((((uintptr_t)x) | ((uintptr_t)y)) & 15))
+    return DVAE_EINVAL;
+  for (int p = 0; p < npairs; ++p) {                // everything the kernel relies on, before any launch
+    const int64_t* q = pairs_host + 4 * p;
+    if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0 || q[1] > ((int64_t)1 << 30) || q[3] > ((int64_t)1 << 30))
+      return DVAE_EINVAL;
+    if (q[1] > 0 && q[3] > 0 && (q[1] < q[3] ? q[1] : q[3]) > DTW_MAX_SHORT) return DVAE_EINVAL;
+  }
+  hipLaunchKernelGGL(dtw_kernel, dim3((unsigned)npairs), dim3(DTW_THREADS), 0, (hipStream_t)stream, x, y, pairs, cost,
+                     length);
   return dvae_check_launch();
 }

@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 309
+#define DVAE_ABI_VERSION 310
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -518,6 +518,36 @@ int dvae_stft_frames_seg(const float* wav, const int64_t* segs, int nseg, int64_
                          float* frames, int fsize, int hop, int left, void* stream);
 int dvae_mel_db_normalize_seg(const float* mel, float* out, const int64_t* segs, int nseg, int64_t rows, int n_mels,
                               float min_level, float ref_level_db, float min_level_db, void* stream);
+
+/* ---- mel-cepstral distortion (python -m dvae_amd.evaluate): preprocessing/MCD_calculate.py:54-103 `evaluate_mcd_wav`
+ * (WORLD mel-cepstra of the voiced frames, fastdtw, mean frame distance along the path) restated on a packed batch
+ * (DESIGN.md §4.6).  The three contractions of the feature pass are dvae_gemm_f32 launches (fp32, unsplit); these are the
+ * passes around them and the alignment.  No atomics, one writer per output element, fixed orders: a pair's bits depend
+ * neither on the batch nor on the run.
+ * dvae_log_power: reim[rows, 2*nbp] (real block | imaginary block) -> power = Re^2 + Im^2, log_power = ln(max(power,
+ *   floor)), both [rows, nbp], 0 in bins nb..nbp; nbp a multiple of 4, all three 16-byte aligned.
+ * dvae_voicing_compact: one workgroup per utterance of `segs` (the dvae_gl_segment_table layout {row0, M, sample0, n} in
+ *   device memory).  r[rows, ldr]: column 0 = the frame's autocorrelation r(0), columns 1..nlag = r at the voicing lags;
+ *   gain[ldr]: r_w(0) / r_w(lag) of the analysis window at the same columns.  peak[row] = max over the lags of r * gain,
+ *   / r(0) (0 where r(0) = 0); voiced[row] = r(0) > 0 and r(0) >= rel_power_min * (max r(0) over the utterance) and
+ *   peak >= peak_min.  The first DVAE_MCD_DIM coefficients of the voiced rows of mc[rows, ldm] go to feats[row0 + k] in
+ *   time order (k = rank among the utterance's voiced frames); count[s] = the number of voiced frames.  mc, feats
+ *   16-byte aligned, ldm a multiple of 4.
+ * dvae_dtw_batch: exact DTW of each pair p of pairs[npairs][4] = {x_row0, nx, y_row0, ny} over rows of DVAE_MCD_DIM floats
+ *   of x and y: D(i,j) = d(i,j) + min(D(i-1,j), D(i,j-1), D(i-1,j-1)), d = the float64 euclidean distance of the fp32
+ *   rows, a tie to the first of the three in that order (fastdtw's); cost[p] = D(nx-1, ny-1), length[p] = cells on that
+ *   path.  nx == 0 or ny == 0: cost NaN, length 0.  `pairs` in device memory and the same table in host memory
+ *   (pairs_host), checked before the launch: DVAE_EINVAL when some pair has min(nx, ny) > DVAE_DTW_MAX_SHORT.  One
+ *   workgroup per pair; x, y 16-byte aligned. */
+#define DVAE_MCD_DIM 24
+#define DVAE_DTW_MAX_SHORT 4096
+int dvae_log_power(const float* reim, float* power, float* log_power, int64_t rows, int nb, int nbp, float floor,
+                   void* stream);
+int dvae_voicing_compact(const float* r, int ldr, int nlag, const float* gain, const float* mc, int ldm,
+                         const int64_t* segs, int nseg, float peak_min, float rel_power_min, float* peak, int* voiced,
+                         float* feats, int* count, void* stream);
+int dvae_dtw_batch(const float* x, const float* y, const int64_t* pairs, const int64_t* pairs_host, int npairs,
+                   double* cost, int64_t* length, void* stream);
 
 /* ---- opt-in per-family kernel timing with HIP events on the launch stream (bench.py roofline) ----
  * family: 0 = off, 1 = GEMM/conv contraction kernel, 2 = LSTM step kernels.
