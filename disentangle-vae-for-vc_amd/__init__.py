@@ -8,6 +8,7 @@ The directory name is not a Python identifier; import it as `dvae_amd` (repo-roo
   _lib.py                  ctypes binding (fails loudly if the library is missing)
   ops.py                   autograd routing between the forward/backward kernels
   model/                   DisentangledVAE, ConvolutionalMulVAE, VariationalBaseModelVAE (reference API)
+  packed.py                the packed-batch layer under the audio tools (frontend, preprocess, evaluate)
   optim.py                 flat-buffer Adam (one HBM-bound launch)
   ddp.py                   bucketed RCCL all-reduce of the flat gradient buffer, overlapped with backward
   data.py                  SpeechDatasetGVAE semantics + synthetic generators

@@ -4,24 +4,6 @@
 
 namespace {
 
-// frames[m][k] = win[k] * x[m*hop + k - left], zero outside the signal (lws pads fsize-hop samples on both sides and
-// the tail up to a whole frame; utils.py:82-103).  One thread writes 4 consecutive k (16-byte stores).
-__global__ void stft_frames_kernel(const float* __restrict__ wav, int64_t n, const float* __restrict__ win,
-                                   float* __restrict__ frames, int M, int fsize, int hop, int left) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int per_row = fsize >> 2;
-  if (idx >= (int64_t)M * per_row) return;
-  const int m = (int)(idx / per_row), k = ((int)(idx - (int64_t)m * per_row)) << 2;
-  const int64_t s = (int64_t)m * hop + k - left;
-  f32x4 v;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int64_t i = s + e;
-    v[e] = (i >= 0 && i < n) ? wav[i] * win[k + e] : 0.f;
-  }
-  *reinterpret_cast<f32x4*>(frames + (int64_t)m * fsize + k) = v;
-}
-
 // reim[row][0..nbp) = Re, [nbp..2nbp) = Im  ->  mag[row][j] = sqrt(Re^2 + Im^2)
 __global__ void stft_magnitude_kernel(const float* __restrict__ reim, float* __restrict__ mag, int64_t rows, int nbp) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -30,26 +12,6 @@ __global__ void stft_magnitude_kernel(const float* __restrict__ reim, float* __r
   const int j = (int)(idx - r * nbp);
   const float re = reim[r * 2 * nbp + j], im = reim[r * 2 * nbp + nbp + j];
   mag[idx] = sqrtf(re * re + im * im);
-}
-
-// out[c][col0 + m] = clip((20*log10(max(min_level, mel[m][c])) - ref_db - min_db) / -min_db, 0, 1)   (utils.py:127-137)
-__global__ void mel_db_normalize_kernel(const float* __restrict__ mel, float* __restrict__ out, int M, int C,
-                                        int64_t ld_out, int64_t col0, float min_level, float ref_db, float min_db) {
-  __shared__ float tile[32][33];
-  const int m0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 256 threads: 8 rows per pass
-  for (int r = ty; r < 32; r += 8) {
-    const int m = m0 + r, c = c0 + tx;
-    tile[r][tx] = (m < M && c < C) ? mel[(int64_t)m * C + c] : 1.f;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int c = c0 + r, m = m0 + tx;
-    if (c < C && m < M) {
-      const float db = 20.f * log10f(fmaxf(min_level, tile[tx][r])) - ref_db;
-      out[(int64_t)c * ld_out + col0 + m] = fminf(fmaxf((db - min_db) / -min_db, 0.f), 1.f);
-    }
-  }
 }
 
 
@@ -393,18 +355,25 @@ __global__ void __launch_bounds__(NV_THREADS) volume_scale_kernel(float* __restr
   }
 }
 
-// stft_frames_kernel over a packed batch: row r of segment {row0, M, sample0, n} (the dvae_gl_segment_table layout) is
-// frame r - row0 of the signal wav[sample0, sample0 + n): the same expression per element
-__global__ void stft_frames_seg_kernel(const float* __restrict__ wav, const int64_t* __restrict__ segs, int nseg,
-                                       int64_t rows, const float* __restrict__ win, float* __restrict__ frames, int fsize,
-                                       int hop, int left) {
+// frames[r][k] = win[k] * x[(r - row0)*hop + k - left], zero outside the signal x = wav[sample0, sample0 + n) (lws pads
+// fsize-hop samples on both sides and the tail up to a whole frame; utils.py:82-103).  Row r belongs to segment
+// {row0, M, sample0, n} of `segs` (the dvae_gl_segment_table layout); segs == nullptr: one utterance, {0, rows, 0,
+// n_one}.  One thread writes 4 consecutive k (16-byte stores).
+__global__ void stft_frames_kernel(const float* __restrict__ wav, const int64_t* __restrict__ segs, int nseg, int64_t n_one,
+                                   int64_t rows, const float* __restrict__ win, float* __restrict__ frames, int fsize,
+                                   int hop, int left) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int per_row = fsize >> 2;
   if (idx >= rows * per_row) return;
   const int64_t r = idx / per_row;
   const int k = ((int)(idx - r * per_row)) << 2;
-  const int sg = find_segment(segs, nseg, r, 0);
-  const int64_t row0 = segs[4 * sg], sample0 = segs[4 * sg + 2], n = segs[4 * sg + 3];
+  int64_t row0 = 0, sample0 = 0, n = n_one;
+  if (segs) {
+    const int sg = find_segment(segs, nseg, r, 0);
+    row0 = segs[4 * sg];
+    sample0 = segs[4 * sg + 2];
+    n = segs[4 * sg + 3];
+  }
   const int64_t s = (r - row0) * hop + k - left;
   f32x4 v;
 #pragma unroll
@@ -415,15 +384,16 @@ __global__ void stft_frames_seg_kernel(const float* __restrict__ wav, const int6
   *reinterpret_cast<f32x4*>(frames + r * fsize + k) = v;
 }
 
-// mel_db_normalize_kernel over a packed batch: mel[rows, C] -> out = the utterances' [C, M] blocks back to back (segment
-// s at C * row0), the same expression per element
-__global__ void mel_db_normalize_seg_kernel(const float* __restrict__ mel, float* __restrict__ out,
-                                            const int64_t* __restrict__ segs, int nseg, int64_t rows, int C,
-                                            float min_level, float ref_db, float min_db) {
+// clip((20*log10(max(min_level, mel[m][c])) - ref_db - min_db) / -min_db, 0, 1) (utils.py:127-137), transposed through a
+// 32 x 33 LDS tile: mel[rows, C] -> the utterances' [C, M] blocks back to back (segment {row0, M, ..} at C * row0);
+// segs == nullptr: one utterance, out[c * ld_one + m] (the host adds col0 to `out`)
+__global__ void mel_db_normalize_kernel(const float* __restrict__ mel, float* __restrict__ out,
+                                        const int64_t* __restrict__ segs, int nseg, int64_t ld_one, int64_t rows, int C,
+                                        float min_level, float ref_db, float min_db) {
   __shared__ float tile[32][33];
   const int64_t m0 = (int64_t)blockIdx.x * 32;
   const int c0 = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 256 threads: 8 rows per pass
   for (int r = ty; r < 32; r += 8) {
     const int64_t m = m0 + r;
     const int c = c0 + tx;
@@ -432,13 +402,17 @@ __global__ void mel_db_normalize_seg_kernel(const float* __restrict__ mel, float
   __syncthreads();
   const int64_t m = m0 + tx;
   if (m >= rows) return;
-  const int sg = find_segment(segs, nseg, m, 0);
-  const int64_t row0 = segs[4 * sg], M = segs[4 * sg + 1];
+  int64_t row0 = 0, ld = ld_one;
+  if (segs) {
+    const int sg = find_segment(segs, nseg, m, 0);
+    row0 = segs[4 * sg];
+    ld = segs[4 * sg + 1];
+  }
   for (int r = ty; r < 32; r += 8) {
     const int c = c0 + r;
     if (c < C) {
       const float db = 20.f * log10f(fmaxf(min_level, tile[tx][r])) - ref_db;
-      out[C * row0 + (int64_t)c * M + (m - row0)] = fminf(fmaxf((db - min_db) / -min_db, 0.f), 1.f);
+      out[C * row0 + (int64_t)c * ld + (m - row0)] = fminf(fmaxf((db - min_db) / -min_db, 0.f), 1.f);
     }
   }
 }
@@ -659,7 +633,7 @@ DVAE_API int dvae_stft_frames(const float* wav, int64_t n, const float* window, 
   if (!wav || !window || !frames || n < 1 || M < 1 || fsize < 4 || (fsize & 3) || hop < 1 || left < 0) return DVAE_EINVAL;
   const int64_t work = (int64_t)M * (fsize >> 2);
   hipLaunchKernelGGL(stft_frames_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     wav, n, window, frames, M, fsize, hop, left);
+                     wav, (const int64_t*)nullptr, 0, n, (int64_t)M, window, frames, fsize, hop, left);
   return dvae_check_launch();
 }
 
@@ -676,8 +650,8 @@ DVAE_API int dvae_mel_db_normalize(const float* mel, float* out, int M, int n_me
   if (!mel || !out || M < 1 || n_mels < 1 || ld_out < M || col0 < 0 || !(min_level > 0.f) || !(min_level_db < 0.f))
     return DVAE_EINVAL;
   dim3 grid((M + 31) / 32, (n_mels + 31) / 32);
-  hipLaunchKernelGGL(mel_db_normalize_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel, out, M, n_mels, ld_out,
-                     col0, min_level, ref_level_db, min_level_db);
+  hipLaunchKernelGGL(mel_db_normalize_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel, out + col0,
+                     (const int64_t*)nullptr, 0, ld_out, (int64_t)M, n_mels, min_level, ref_level_db, min_level_db);
   return dvae_check_launch();
 }
 
@@ -824,8 +798,8 @@ DVAE_API int dvae_stft_frames_seg(const float* wav, const int64_t* segs, int nse
       (((uintptr_t)frames) & 15))
     return DVAE_EINVAL;
   const int64_t work = rows * (fsize >> 2);
-  hipLaunchKernelGGL(stft_frames_seg_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     wav, segs, nseg, rows, window, frames, fsize, hop, left);
+  hipLaunchKernelGGL(stft_frames_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     wav, segs, nseg, (int64_t)0, rows, window, frames, fsize, hop, left);
   return dvae_check_launch();
 }
 
@@ -835,8 +809,8 @@ DVAE_API int dvae_mel_db_normalize_seg(const float* mel, float* out, const int64
       !(min_level_db < 0.f))
     return DVAE_EINVAL;
   dim3 grid((unsigned)((rows + 31) / 32), (n_mels + 31) / 32);
-  hipLaunchKernelGGL(mel_db_normalize_seg_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel, out, segs, nseg, rows,
-                     n_mels, min_level, ref_level_db, min_level_db);
+  hipLaunchKernelGGL(mel_db_normalize_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel, out, segs, nseg,
+                     (int64_t)0, rows, n_mels, min_level, ref_level_db, min_level_db);
   return dvae_check_launch();
 }
 

@@ -22,8 +22,8 @@ pyworld, pysptk, fastdtw and librosa are absent, so the score is defined here (D
     MCD        10/ln10 * sqrt(2) * cost / length (float64, host); a side without voiced frames gives NaN, reported and
                left out of the mean (the reference would raise inside fastdtw)
 
-Every utterance of a batch is packed row-wise (preprocess.pack) and runs in one launch per pass; the contractions are pinned
-to fp32 and one k-split (the MelFrontend._gemm pattern), so an utterance's features and a pair's score are bit-identical
+Every utterance of a batch is packed row-wise (packed.pack) and runs in one launch per pass; the contractions are pinned
+to fp32 and one k-split (packed.pinned_gemm), so an utterance's features and a pair's score are bit-identical
 whatever else shares the batch.  GPU only, no CPU fallback.
 """
 from __future__ import annotations
@@ -36,6 +36,13 @@ from pathlib import Path
 from typing import Sequence
 
 import numpy as np
+import torch
+
+from . import packed
+from ._lib import check, lib, ptr, stream
+from .frontend import dft_basis
+from .packed import flat, onesided_dft, pack, pack_rows, pad4, padded_bins, pinned_gemm, segment_table, upload
+from .preprocess import Resampler, read_wav, resample_batch
 
 SAMPLE_RATE = 16000
 HOP = 80                      # 5 ms
@@ -54,18 +61,9 @@ DTW_MAX_SHORT = 4096          # DVAE_DTW_MAX_SHORT: min(N, M) the DTW kernel sup
 MCD_SCALE = 10.0 / math.log(10.0) * math.sqrt(2.0)
 
 
-def _nbp(fft_size=FFT_SIZE):
-    return (fft_size // 2 + 1 + 3) // 4 * 4
-
-
-def _pad4(n):
-    return (n + 3) // 4 * 4
-
-
 # ------------------------------------------------------------------------------------------------ host tables (float64)
 def hann_periodic(n: int = FRAME) -> np.ndarray:
-    k = np.arange(n, dtype=np.float64)
-    return 0.5 - 0.5 * np.cos(2.0 * np.pi * k / n)
+    return packed.hann_periodic(n)
 
 
 def lags() -> np.ndarray:
@@ -75,11 +73,7 @@ def lags() -> np.ndarray:
 
 def irfft_matrix(fft_size: int = FFT_SIZE) -> np.ndarray:
     """[fft_size, nb]: c = irfft(X) of a real spectrum X over the nb = fft_size/2 + 1 one-sided bins (np.fft.irfft)"""
-    nb = fft_size // 2 + 1
-    w = np.full(nb, 2.0)
-    w[0] = w[-1] = 1.0
-    ang = 2.0 * np.pi * np.outer(np.arange(fft_size, dtype=np.float64), np.arange(nb, dtype=np.float64)) / fft_size
-    return w * np.cos(ang) / fft_size
+    return onesided_dft(fft_size, inverse=True)[0]
 
 
 def freqt_matrix(m1: int, m2: int, alpha: float) -> np.ndarray:
@@ -109,10 +103,7 @@ def sp2mc_matrix(order: int = ORDER, alpha: float = ALPHA, fft_size: int = FFT_S
 def lag_basis(fft_size: int = FFT_SIZE) -> np.ndarray:
     """[len(lags()), nb] float64: r(tau) = L @ P is the autocorrelation of the zero-padded frame at the lags (the inverse
     DFT of the power spectrum; no wrap-around while tau + FRAME <= fft_size)"""
-    nb = fft_size // 2 + 1
-    w = np.full(nb, 2.0)
-    w[0] = w[-1] = 1.0
-    return w * np.cos(2.0 * np.pi * np.outer(lags(), np.arange(nb)) / fft_size) / fft_size
+    return onesided_dft(fft_size, rows=lags(), inverse=True)[0]
 
 
 def window_gain() -> np.ndarray:
@@ -136,51 +127,33 @@ def mcd_from(cost, length):
 
 
 # ------------------------------------------------------------------------------------------------------------ GPU passes
-def _dev():
-    import torch
-    from ._lib import check, lib, ptr, stream
-    return torch, check, lib, ptr, stream
-
-
 class MelCepstrum:
     """The feature pass on the GPU: waveforms -> per frame 24 mel-cepstral coefficients and a voicing flag; one launch per
     pass for a whole packed batch (framing, DFT contraction, log power, mcep and lag contractions, voicing + compaction).
     Tables are built once (float64 on the host, fp32 on the device)."""
 
     def __init__(self, device="cuda"):
-        import torch
-        from . import ops
-        from .frontend import dft_basis
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("MelCepstrum runs on the HIP path only (no CPU fallback)")
-        self.nb, self.nbp = FFT_SIZE // 2 + 1, _nbp()
-        self.n_mc, self.n_lag = _pad4(ORDER + 1), _pad4(len(lags()))          # 40, 208 rows (16-byte rows)
+        self.nb, self.nbp = FFT_SIZE // 2 + 1, padded_bins(FFT_SIZE)
+        self.n_mc, self.n_lag = pad4(ORDER + 1), pad4(len(lags()))          # 40, 208 rows (16-byte rows)
         mc = np.zeros((self.n_mc, self.nbp))
         mc[:ORDER + 1, :self.nb] = sp2mc_matrix()
         lg = np.zeros((self.n_lag, self.nbp))
         lg[:len(lags()), :self.nb] = lag_basis()
         gain = np.zeros(self.n_lag)
         gain[:len(lags())] = window_gain()
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+        f32 = lambda a: upload(a, self.device)
         self.window = f32(hann_periodic())
         self.dft = f32(dft_basis(FFT_SIZE, self.nbp)[:, :FRAME])                # [2 nbp, 512]: the padded half is zero
         self.mc_basis, self.lag_basis, self.gain = f32(mc), f32(lg), f32(gain)
-        self.mode = ops.MODE_F32
         self._resampler = None
-
-    def _gemm(self, A, B, C, K):
-        # C[rows, N] = A[rows, K] B[N, K]^T, fp32 products, ONE k-split whatever the row count (MelFrontend._gemm)
-        from . import ops
-        ops.gemm(A, B, C, None, A.shape[0], B.shape[0], K, K, K, B.shape[0], True, True, ops.ACT_NONE, ops.EPI_STORE, 1,
-                 self.mode)
 
     def to16k(self, wavs: Sequence, srs: Sequence[int] = None) -> list:
         """1-D waveforms (numpy / tensors) at `srs` (default all 16 kHz) -> 1-D fp32 arrays / device tensors at 16 kHz
         (preprocess.resample_batch: one launch for those at other rates)"""
-        torch = _dev()[0]
-        from .preprocess import Resampler, resample_batch
-        wavs = [w.reshape(-1) if torch.is_tensor(w) else np.asarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+        wavs = [flat(w) for w in wavs]
         if srs is None:
             return wavs
         if len(srs) != len(wavs):
@@ -202,8 +175,6 @@ class MelCepstrum:
           count   [nseg] int64 numpy (one sync)
           mc      [rows, 40] device: every frame's coefficients (0..35; 36..39 zero)
           voiced  [rows] int32 device;  peak [rows] device: max r_n;  r [rows, 208] device: r(0), r(20..225)"""
-        torch, check, lib, ptr, stream = _dev()
-        from .preprocess import pack
         L = lib()
         sigs = self.to16k(wavs, srs)
         if not sigs:
@@ -211,27 +182,23 @@ class MelCepstrum:
         ns = [int(s.shape[0]) for s in sigs]
         wav, offs = pack(sigs, self.device)
         ms = [frame_count(n) for n in ns]
-        table = np.zeros((len(ns), 4), dtype=np.int64)
-        table[:, 0] = np.concatenate([[0], np.cumsum(ms)[:-1]])
-        table[:, 1] = ms
-        table[:, 2] = offs
-        table[:, 3] = ns
-        segs = torch.from_numpy(table).to(self.device)
+        table = segment_table(ms, offs, ns)
+        segs = upload(table, self.device, np.int64)
         rows, nseg = int(sum(ms)), len(ns)
         f = lambda *shape: torch.empty(shape, device=self.device, dtype=torch.float32)
         frames = f(rows, FRAME)
         check(L.dvae_stft_frames_seg(ptr(wav), ptr(segs), nseg, rows, ptr(self.window), ptr(frames), FRAME, HOP,
                                      FRAME // 2, stream()), "dvae_stft_frames_seg")
         reim = f(rows, 2 * self.nbp)
-        self._gemm(frames, self.dft, reim, FRAME)
+        pinned_gemm(frames, self.dft, reim, FRAME)
         del frames
         pw, lp = f(rows, self.nbp), f(rows, self.nbp)
         check(L.dvae_log_power(ptr(reim), ptr(pw), ptr(lp), rows, self.nb, self.nbp, POWER_FLOOR, stream()),
               "dvae_log_power")
         del reim
         mc, r = f(rows, self.n_mc), f(rows, self.n_lag)
-        self._gemm(lp, self.mc_basis, mc, self.nbp)
-        self._gemm(pw, self.lag_basis, r, self.nbp)
+        pinned_gemm(lp, self.mc_basis, mc, self.nbp)
+        pinned_gemm(pw, self.lag_basis, r, self.nbp)
         del pw, lp
         feats, peak = f(rows, DIM), f(rows)
         voiced = torch.empty(rows, device=self.device, dtype=torch.int32)
@@ -260,11 +227,10 @@ def check_pairs(nx, ny, names=None):
 
 def _dtw_launch(x, y, pairs, names=None):
     """pairs [P, 4] int64 numpy {x_row0, nx, y_row0, ny} into device buffers x, y [., 24] -> (cost, length) numpy"""
-    torch, check, lib, ptr, stream = _dev()
     pairs = np.ascontiguousarray(pairs, dtype=np.int64)
     check_pairs(pairs[:, 1], pairs[:, 3], names)
     dev = x.device
-    pd = torch.from_numpy(pairs).to(dev)
+    pd = upload(pairs, dev, np.int64)
     cost = torch.empty(len(pairs), device=dev, dtype=torch.float64)
     length = torch.empty(len(pairs), device=dev, dtype=torch.int64)
     check(lib().dvae_dtw_batch(ptr(x), ptr(y), ptr(pd), pairs.ctypes.data, len(pairs), ptr(cost), ptr(length), stream()),
@@ -275,21 +241,10 @@ def _dtw_launch(x, y, pairs, names=None):
 def dtw_batch(xs: Sequence, ys: Sequence, device="cuda"):
     """exact DTW of every pair (xs[p] [N_p, 24], ys[p] [M_p, 24]) in one launch -> (cost float64 [P], length int64 [P]);
     cost NaN and length 0 where a side is empty"""
-    torch = _dev()[0]
     if len(xs) != len(ys) or not xs:
         raise ValueError("dtw_batch: one y per x, at least one pair")
-
-    def packrows(seqs):
-        arrs = [np.asarray(s, dtype=np.float32).reshape(-1, DIM) for s in seqs]
-        n = [a.shape[0] for a in arrs]
-        row0 = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
-        host = np.zeros((max(1, sum(n)), DIM), dtype=np.float32)
-        for a, r in zip(arrs, row0):
-            host[r:r + a.shape[0]] = a
-        return torch.from_numpy(host).to(device), row0, n
-
-    x, xr, nx = packrows(xs)
-    y, yr, ny = packrows(ys)
+    x, xr, nx = pack_rows([np.asarray(s, dtype=np.float32).reshape(-1, DIM) for s in xs], DIM, device)
+    y, yr, ny = pack_rows([np.asarray(s, dtype=np.float32).reshape(-1, DIM) for s in ys], DIM, device)
     pairs = np.stack([xr, nx, yr, ny], axis=1).astype(np.int64)
     return _dtw_launch(x, y, pairs)
 
@@ -357,7 +312,6 @@ def _parse(argv):
 
 
 def main(argv=None) -> int:
-    from .preprocess import read_wav
     args = _parse(sys.argv[1:] if argv is None else argv)
     for d in (args.converted_dir, args.reference_dir):
         if not d.is_dir():

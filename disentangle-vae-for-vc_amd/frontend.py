@@ -28,6 +28,8 @@ import torch
 
 from . import ops
 from ._lib import check, lib, ptr, stream
+from .packed import (flat, hann_periodic, onesided_dft, pack, pack_rows, padded_bins, pinned_gemm, segment_table,
+                     split_rows, upload)
 
 
 def _slaney_hz_to_mel(f):
@@ -42,18 +44,16 @@ def _slaney_mel_to_hz(m):
 
 def lws_window(fft_size: int, hop_size: int) -> np.ndarray:
     """lws "speech" analysis (and synthesis) window: sqrt(periodic Hann * 2*hop/fsize), float64 [fsize]."""
-    n = np.arange(fft_size, dtype=np.float64)
-    return np.sqrt((0.5 - 0.5 * np.cos(2.0 * np.pi * n / fft_size)) * 2.0 * hop_size / fft_size)
+    return np.sqrt(hann_periodic(fft_size) * 2.0 * hop_size / fft_size)
 
 
 def dft_basis(fft_size: int, nbp: int) -> np.ndarray:
     """One-sided forward DFT basis, float64 [2*nbp, fsize]: rows [0, nb) cos, rows [nbp, nbp+nb) -sin, padded bins 0."""
     nb = fft_size // 2 + 1
-    n = np.arange(fft_size, dtype=np.float64)
-    ang = 2.0 * np.pi * np.outer(np.arange(nb, dtype=np.float64), n) / fft_size
+    cos, sin = onesided_dft(fft_size)
     basis = np.zeros((2 * nbp, fft_size), dtype=np.float64)
-    basis[:nb] = np.cos(ang)
-    basis[nbp:nbp + nb] = -np.sin(ang)
+    basis[:nb] = cos.T
+    basis[nbp:nbp + nb] = -sin.T
     return basis
 
 
@@ -83,12 +83,10 @@ class MelFrontend:
         self.min_level_db, self.ref_level_db = float(min_level_db), float(ref_level_db)
         self.min_level = float(np.exp(min_level_db / 20.0 * np.log(10.0)))  # utils.py:128
         nb = fft_size // 2 + 1
-        self.nb, self.nbp = nb, (nb + 3) // 4 * 4
-        win = lws_window(fft_size, hop_size)
-        basis = dft_basis(fft_size, self.nbp)
-        melw = mel_basis(sample_rate, fft_size, num_mels, fmin, fmax, self.nbp)
-        f32 = lambda a: torch.from_numpy(a.astype(np.float32)).to(self.device).contiguous()
-        self.window, self.dft_basis, self.mel_basis = f32(win), f32(basis), f32(melw)
+        self.nb, self.nbp = nb, padded_bins(fft_size)
+        self.window = upload(lws_window(fft_size, hop_size), self.device)
+        self.dft_basis = upload(dft_basis(fft_size, self.nbp), self.device)
+        self.mel_basis = upload(mel_basis(sample_rate, fft_size, num_mels, fmin, fmax, self.nbp), self.device)
         self.mode = ops.MODE_F32
 
     # ---- utils.py:82-103
@@ -98,74 +96,43 @@ class MelFrontend:
         return (length + 2 * pad - self.fsize) // self.hop + extra
 
     def melspectrogram_batch(self, wavs: Sequence, unsplit: bool = False) -> list:
-        """List of 1-D waveforms (numpy / tensors, any length >= 1) -> list of device tensors [80, M_i].
-        unsplit=True: the pinned path of the corpus tool (preprocess.py): both contractions with ONE k-split and the
-        segmented framing / dB passes, so that an utterance's mel is bit-identical whatever batch it lands in (the default
-        lets the contraction pick a split from the row count)."""
-        L = lib()
-        sigs = [torch.as_tensor(np.asarray(w, dtype=np.float32) if not torch.is_tensor(w) else w)
-                .to(self.device, torch.float32).contiguous().view(-1) for w in wavs]
-        if not sigs or any(s.numel() < 1 for s in sigs):
-            raise ValueError("melspectrogram: empty waveform")
-        if unsplit:
-            from .preprocess import pack
-            wav, offs = pack(sigs, self.device)
-            out, ms = self._mel_packed(wav, offs, [s.numel() for s in sigs])
-            return self.unpack(out, ms)
-        ms = [self.num_frames(s.numel()) for s in sigs]
-        rows = sum(ms)
-        frames = torch.empty((rows, self.fsize), device=self.device, dtype=torch.float32)
-        r = 0
-        for s, m in zip(sigs, ms):
-            check(L.dvae_stft_frames(ptr(s), s.numel(), ptr(self.window), frames[r:].data_ptr(), m, self.fsize,
-                                     self.hop, self.fsize - self.hop, stream()), "dvae_stft_frames")
-            r += m
+        """List of 1-D waveforms (numpy / tensors, any length >= 1) -> list of device tensors [80, M_i] (views of one
+        packed buffer).  unsplit=True: the pinned path of the corpus tool (preprocess.py): both contractions with ONE
+        k-split, so that an utterance's mel is bit-identical whatever batch it lands in (the default lets the
+        contraction pick a split from the row count)."""
+        sigs = [flat(w) for w in wavs]
+        wav, offs = pack(sigs, self.device)
+        return self.unpack(*self.mel_packed(wav, offs, [s.shape[0] for s in sigs], pinned=unsplit))
+
+    def _contract(self, A, B, K, pinned):
         # features must not depend on the training compute mode (bf16 would put a leakage floor ~50 dB under each frame's
-        # peak against a 100 dB normalisation range): both contractions are pinned to exact fp32 products
-        reim = ops.linear_fwd(frames, self.dft_basis, None, mode=self.mode)  # [rows, 2*nbp]
-        mag = torch.empty((rows, self.nbp), device=self.device, dtype=torch.float32)
-        check(L.dvae_stft_magnitude(ptr(reim), ptr(mag), rows, self.nbp, stream()), "dvae_stft_magnitude")
-        mel = ops.linear_fwd(mag, self.mel_basis, None, mode=self.mode)      # [rows, 80]
-        outs, r = [], 0
-        for m in ms:
-            out = torch.empty((self.n_mels, m), device=self.device, dtype=torch.float32)
-            check(L.dvae_mel_db_normalize(mel[r:].data_ptr(), ptr(out), m, self.n_mels, m, 0, self.min_level,
-                                          self.ref_level_db, self.min_level_db, stream()), "dvae_mel_db_normalize")
-            outs.append(out)
-            r += m
-        return outs
+        # peak against a 100 dB normalisation range): exact fp32 products either way; only the k-split differs
+        if not pinned:
+            return ops.linear_fwd(A, B, None, mode=self.mode)
+        C = torch.empty((A.shape[0], B.shape[0]), device=self.device, dtype=torch.float32)
+        pinned_gemm(A, B, C, K)
+        return C
 
-    def _gemm(self, A, B, C, K):
-        # C[rows, N] = A[rows, K] B[N, K]^T, fp32 products, ONE k-split whatever the row count (MelInverter._gemm)
-        ops.gemm(A, B, C, None, A.shape[0], B.shape[0], K, K, K, B.shape[0], True, True, ops.ACT_NONE, ops.EPI_STORE, 1,
-                 self.mode)
-
-    def _mel_packed(self, wav, sample0, lengths):
-        """Pinned mel of the signals wav[sample0[i], sample0[i] + lengths[i]) of one device buffer: five launches for the
-        whole batch -> (packed out: the [80, M_i] blocks back to back, [M_i])"""
+    def mel_packed(self, wav, sample0, lengths, pinned=True):
+        """Mel of the signals wav[sample0[i], sample0[i] + lengths[i]) of one device buffer: five launches for the whole
+        batch -> (packed out: the [80, M_i] blocks back to back, [M_i]).  `pinned` selects how the two contractions run
+        and nothing else."""
         L = lib()
         ns = [int(n) for n in lengths]
         if not ns or min(ns) < 1:
             raise ValueError("melspectrogram: empty waveform")
         ms = [self.num_frames(n) for n in ns]
-        table = np.zeros((len(ns), 4), dtype=np.int64)          # {row0, M, sample0, n}: dvae_gl_segment_table's layout
-        table[:, 0] = np.concatenate([[0], np.cumsum(ms)[:-1]])
-        table[:, 1] = ms
-        table[:, 2] = np.asarray(sample0, dtype=np.int64)
-        table[:, 3] = ns
-        segs = torch.from_numpy(table).to(self.device)
+        segs = upload(segment_table(ms, sample0, ns), self.device, np.int64)
         rows = int(sum(ms))
         frames = torch.empty((rows, self.fsize), device=self.device, dtype=torch.float32)
         check(L.dvae_stft_frames_seg(ptr(wav), ptr(segs), len(ns), rows, ptr(self.window), ptr(frames), self.fsize,
                                      self.hop, self.fsize - self.hop, stream()), "dvae_stft_frames_seg")
-        reim = torch.empty((rows, 2 * self.nbp), device=self.device, dtype=torch.float32)
-        self._gemm(frames, self.dft_basis, reim, self.fsize)
+        reim = self._contract(frames, self.dft_basis, self.fsize, pinned)        # [rows, 2*nbp]
         del frames
         mag = torch.empty((rows, self.nbp), device=self.device, dtype=torch.float32)
         check(L.dvae_stft_magnitude(ptr(reim), ptr(mag), rows, self.nbp, stream()), "dvae_stft_magnitude")
         del reim
-        mel = torch.empty((rows, self.n_mels), device=self.device, dtype=torch.float32)
-        self._gemm(mag, self.mel_basis, mel, self.nbp)
+        mel = self._contract(mag, self.mel_basis, self.nbp, pinned)             # [rows, 80]
         out = torch.empty(rows * self.n_mels, device=self.device, dtype=torch.float32)
         check(L.dvae_mel_db_normalize_seg(ptr(mel), ptr(out), ptr(segs), len(ns), rows, self.n_mels, self.min_level,
                                           self.ref_level_db, self.min_level_db, stream()), "dvae_mel_db_normalize_seg")
@@ -173,11 +140,7 @@ class MelFrontend:
 
     def unpack(self, out, ms):
         """packed [80, M_i] blocks (a device or host tensor / array) -> list of [80, M_i] views"""
-        res, r = [], 0
-        for m in ms:
-            res.append(out[self.n_mels * r:self.n_mels * (r + m)].reshape(self.n_mels, m))
-            r += m
-        return res
+        return [blk.reshape(self.n_mels, m) for blk, m in zip(split_rows(out, [self.n_mels * m for m in ms]), ms)]
 
     def melspectrogram(self, wav):
         """One waveform -> [80, M] in [0, 1] (utils.py:68-73)."""
@@ -197,19 +160,13 @@ def inverse_tables(sample_rate=16000, fft_size=1024, hop_size=256, num_mels=80, 
       bin_filt   [nbp, 2] int32    per bin at most two filters (-1: none) ...
       bin_w      [nbp, 2]          ... and their weights (Slaney triangles overlap their neighbours only)
       ola_norm   bool              the squared window does NOT overlap-add to 1 at this hop: divide by the envelope"""
-    nb = fft_size // 2 + 1
-    nbp = (nb + 3) // 4 * 4
+    nb, nbp = fft_size // 2 + 1, padded_bins(fft_size)
     win = lws_window(fft_size, hop_size)
     melw = mel_basis(sample_rate, fft_size, num_mels, fmin, fmax, nbp)
-    k = np.arange(fft_size, dtype=np.float64)
-    ang = 2.0 * np.pi * np.outer(k, np.arange(nb, dtype=np.float64)) / fft_size      # [fsize, nb]
-    c = np.full(nb, 2.0)
-    c[0] = 1.0
-    if fft_size % 2 == 0:
-        c[-1] = 1.0
+    cos, sin = onesided_dft(fft_size, inverse=True)                                  # [fsize, nb]
     inv = np.zeros((fft_size, 2 * nbp), dtype=np.float64)
-    inv[:, :nb] = c / fft_size * np.cos(ang)
-    inv[:, nbp:nbp + nb] = -c / fft_size * np.sin(ang)
+    inv[:, :nb] = cos
+    inv[:, nbp:nbp + nb] = -sin
     pinv = np.linalg.pinv(melw)
     step = 1.0 / float(np.linalg.norm(melw, 2)) ** 2
     rng = np.zeros((num_mels, 2), dtype=np.int32)
@@ -271,12 +228,11 @@ class MelInverter:
         self.min_frames = fft_size // hop_size
         t = inverse_tables(sample_rate, fft_size, hop_size, num_mels, fmin, fmax)
         self.nb, self.nbp, self.step, self.ola_norm = t["nb"], t["nbp"], float(t["step"]), int(t["ola_norm"])
-        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
-        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+        f32 = lambda a: upload(a, self.device)
+        i32 = lambda a: upload(a, self.device, np.int32)
         self.window, self.inv_basis, self.pinv = f32(t["window"]), f32(t["inv_basis"]), f32(t["pinv"])
         self.dft_basis = f32(dft_basis(fft_size, self.nbp))
         self.filt_range, self.bin_filt, self.bin_w = i32(t["filt_range"]), i32(t["bin_filt"]), f32(t["bin_w"])
-        self.mode = ops.MODE_F32
 
     def num_samples(self, frames: int) -> int:
         """M frames -> n samples, with lws_num_frames(n) == M"""
@@ -288,11 +244,6 @@ class MelInverter:
         bad = [m for m in counts if m < self.min_frames]
         if bad:
             raise ValueError(f"MelInverter: {bad[0]} frames; the inverse needs >= {self.min_frames} (fft_size / hop_size)")
-
-    def _gemm(self, A, B, C, K, act=ops.ACT_NONE):
-        # C[rows, N] = act(A[rows, K] B[N, K]^T): fp32 products, ONE k-split whatever the row count (bits of a row
-        # independent of the batch it shares a launch with, of the compute mode and of ops.set_deterministic)
-        ops.gemm(A, B, C, None, A.shape[0], B.shape[0], K, K, K, B.shape[0], True, True, act, ops.EPI_STORE, 1, self.mode)
 
     def _magnitude(self, mels):
         """list of [80, M_i] -> (X [rows, nbp] device, [M_i])"""
@@ -308,7 +259,7 @@ class MelInverter:
         check(L.dvae_mel_denormalize(ptr(mel), ptr(amp), rows, self.n_mels, rows, self.ref_level_db, self.min_level_db,
                                      stream()), "dvae_mel_denormalize")
         x = torch.empty((rows, self.nbp), device=self.device, dtype=torch.float32)
-        self._gemm(amp, self.pinv, x, self.n_mels, act=ops.ACT_RELU)
+        pinned_gemm(amp, self.pinv, x, self.n_mels, act=ops.ACT_RELU)
         check(L.dvae_mel_nnls_pg(ptr(amp), ptr(x), rows, self.nbp, self.n_mels, ptr(self.filt_range), ptr(self.bin_filt),
                                  ptr(self.bin_w), self.step, self.nnls_iter, stream()), "dvae_mel_nnls_pg")
         return x, counts
@@ -316,11 +267,7 @@ class MelInverter:
     def linear_magnitude_batch(self, mels: Sequence) -> list:
         """list of [80, M_i] normalised mels -> list of device tensors [M_i, fft_size//2 + 1] (frame-major |STFT|)"""
         x, counts = self._magnitude(mels)
-        out, r = [], 0
-        for m in counts:
-            out.append(x[r:r + m, :self.nb])
-            r += m
-        return out
+        return split_rows(x[:, :self.nb], counts)
 
     def griffinlim_batch(self, mags: Sequence, n_iter=None, init="random", generator=None, init_phase=None) -> list:
         """list of [M_i, nb] (or [M_i, nbp]) linear magnitudes -> list of 1-D device waveforms of num_samples(M_i).
@@ -334,23 +281,15 @@ class MelInverter:
         counts = [int(m.shape[0]) for m in ms]
         self._frames_of(counts)
         rows, nbp, fs = sum(counts), self.nbp, self.fsize
-        S = torch.zeros((rows, nbp), device=self.device, dtype=torch.float32)
-        r = 0
-        for m, c in zip(ms, counts):
-            if m.dim() != 2 or m.shape[1] not in (self.nb, nbp):
-                raise ValueError(f"MelInverter: magnitudes must be [M, {self.nb}]")
-            S[r:r + c, :m.shape[1]] = m
-            r += c
+        if any(m.dim() != 2 or m.shape[1] not in (self.nb, nbp) for m in ms):
+            raise ValueError(f"MelInverter: magnitudes must be [M, {self.nb}]")
+        S = pack_rows(ms, nbp, self.device)[0]
         phase = None
         if init_phase is not None:
-            phase = torch.zeros((rows, nbp), device=self.device, dtype=torch.float32)
-            r = 0
-            for p, c in zip(init_phase, counts):
-                p = torch.as_tensor(p).to(self.device, torch.float32)
-                if p.shape[0] != c:
-                    raise ValueError("MelInverter: init_phase rows differ from the magnitudes'")
-                phase[r:r + c, :p.shape[1]] = p
-                r += c
+            ps = [torch.as_tensor(p).to(self.device, torch.float32) for p in init_phase]
+            if [int(p.shape[0]) for p in ps] != counts:
+                raise ValueError("MelInverter: init_phase rows differ from the magnitudes'")
+            phase = pack_rows(ps, nbp, self.device)[0]
         elif init == "random":
             gdev = generator.device if generator is not None else self.device
             phase = (2.0 * math.pi) * torch.rand((rows, nbp), generator=generator, device=gdev, dtype=torch.float32)
@@ -370,14 +309,14 @@ class MelInverter:
         reb, prev = torch.empty_like(X), torch.empty_like(X)
         nseg = len(counts)
         for it in range(n_iter):
-            self._gemm(X, self.inv_basis, y, 2 * nbp)
+            pinned_gemm(X, self.inv_basis, y, 2 * nbp)
             check(L.dvae_ola_gather(ptr(y), ptr(segs), nseg, rows, ptr(self.window), ptr(frames), 0, fs, self.hop, 0,
                                     self.ola_norm, stream()), "dvae_ola_gather")
-            self._gemm(frames, self.dft_basis, reb, fs)
+            pinned_gemm(frames, self.dft_basis, reb, fs)
             check(L.dvae_gl_phase(ptr(reb), ptr(prev) if it else None, ptr(S), ptr(X), rows, nbp, self.momentum, stream()),
                   "dvae_gl_phase")
             reb, prev = prev, reb
-        self._gemm(X, self.inv_basis, y, 2 * nbp)
+        pinned_gemm(X, self.inv_basis, y, 2 * nbp)
         wav = torch.empty(n_total, device=self.device, dtype=torch.float32)
         check(L.dvae_ola_gather(ptr(y), ptr(segs), nseg, rows, ptr(self.window), ptr(wav), n_total, fs, self.hop, 1,
                                 self.ola_norm, stream()), "dvae_ola_gather")
@@ -386,11 +325,7 @@ class MelInverter:
     def waveform_batch(self, mels: Sequence, n_iter=None, init="random", generator=None, init_phase=None) -> list:
         """list of [80, M_i] normalised mels (the corpus layout) -> list of 1-D device waveforms of (M_i - 3) * hop samples"""
         x, counts = self._magnitude(mels)
-        out, r = [], 0
-        for m in counts:
-            out.append(x[r:r + m])
-            r += m
-        return self.griffinlim_batch(out, n_iter=n_iter, init=init, generator=generator, init_phase=init_phase)
+        return self.griffinlim_batch(split_rows(x, counts), n_iter=n_iter, init=init, generator=generator, init_phase=init_phase)
 
     def waveform(self, mel, **kw):
         """One [80, M] mel -> 1-D device waveform"""

@@ -35,6 +35,11 @@ from pathlib import Path
 from typing import Sequence
 
 import numpy as np
+import torch
+
+from ._lib import check, lib, ptr, stream
+from .frontend import MelFrontend
+from .packed import flat, pack, pad4, upload  # noqa: F401  (pack: its callers import it from here too)
 
 SAMPLE_RATE = 16000
 RESAMPLE_TILE = 256           # DVAE_RESAMPLE_TILE
@@ -190,18 +195,11 @@ def resample_filter(sr_old: int, sr_new: int = SAMPLE_RATE) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------------------ GPU passes
-def _dev():
-    import torch
-    from ._lib import check, lib, ptr, stream
-    return torch, check, lib, ptr, stream
-
-
 class Resampler:
     """Packed-batch resampler to `sr_new` on the GPU (dvae_resample_batch): one launch for utterances of any source rates
     and lengths.  The per-phase float64 weights of each source rate are rounded to fp32 once and kept on the device."""
 
     def __init__(self, device="cuda", sr_new: int = SAMPLE_RATE):
-        import torch
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("Resampler runs on the HIP path only (no CPU fallback)")
@@ -212,7 +210,6 @@ class Resampler:
     def _filter(self, sr_old: int) -> int:
         sr_old = int(sr_old)
         if sr_old not in self._ids:
-            _, _, lib, _, _ = _dev()
             if sr_old == self.sr_new:                  # the identity inside a packed batch: y = fmaf(1, x, 0) = x
                 P, Q, base, taps, w = 1, 1, 0, 1, np.ones(1, dtype=np.float32)
             else:
@@ -230,16 +227,14 @@ class Resampler:
         return self._ids[sr_old]
 
     def _tables(self):
-        torch = _dev()[0]
         if self._weights is None:
-            self._weights = torch.from_numpy(np.concatenate(self._chunks)).to(self.device)
-            self._filters = torch.from_numpy(np.asarray(self._rows, dtype=np.int64)).to(self.device)
+            self._weights = upload(np.concatenate(self._chunks), self.device)
+            self._filters = upload(self._rows, self.device, np.int64)
         return self._weights, self._filters
 
     def plan(self, lengths: Sequence[int], srs: Sequence[int], tile=RESAMPLE_TILE):
         """-> (table [nseg, 6] int64 {in0, n_in, out0, n_out, n_valid, filter}, tiles [ntiles, 2] int64, filter ids);
         ValueError when an utterance is too short for resampy (int(n * ratio) < 1)"""
-        _, check, lib, _, _ = _dev()
         for n, sr in zip(lengths, srs):
             if n < 1 or (sr != self.sr_new and resample_lengths(n, sr, self.sr_new)[0] < 1):
                 raise ValueError(f"resample: {n} samples at {sr} Hz is too short to resample to {self.sr_new} Hz")
@@ -258,17 +253,15 @@ class Resampler:
 
     def prepare(self, lengths: Sequence[int], srs: Sequence[int]) -> dict:
         """the host side of a launch: plan(), the tables on the device, the LDS size, the output length"""
-        torch = _dev()[0]
         table, tiles, fid = self.plan(lengths, srs)
         self._tables()
-        segs_d, tiles_d = (torch.from_numpy(a).to(self.device) for a in (table, tiles))
+        segs_d, tiles_d = (upload(a, self.device, np.int64) for a in (table, tiles))
         return dict(table=table, ntiles=len(tiles), segs=segs_d, tiles=tiles_d,
                     lds=max(self._lds[i] for i in set(fid.tolist())),
-                    n_out=int(table[-1, 2] + ((table[-1, 3] + 3) // 4) * 4))
+                    n_out=int(table[-1, 2] + pad4(table[-1, 3])))
 
     def launch(self, x, prep: dict, y=None):
         """dvae_resample_batch alone on prepared tables (prep holds them on the device until it is dropped)"""
-        torch, check, lib, ptr, stream = _dev()
         weights, filters = self._tables()
         if y is None:
             y = torch.empty(prep["n_out"], device=self.device, dtype=torch.float32)
@@ -285,33 +278,11 @@ class Resampler:
         return resample_batch(wavs, srs, self.sr_new, resampler=self)
 
 
-def pack(arrays: Sequence, device="cuda"):
-    """list of 1-D float32 arrays / tensors -> (device fp32 buffer, offsets): each starts at a multiple of 4 elements (the
-    packing of dvae_resample_segment_table)"""
-    torch = _dev()[0]
-    ns = [int(a.shape[0]) for a in arrays]
-    offs = np.zeros(len(ns), dtype=np.int64)
-    tot = 0
-    for i, n in enumerate(ns):
-        offs[i] = tot
-        tot += (n + 3) // 4 * 4
-    if all(not torch.is_tensor(a) for a in arrays):
-        host = np.zeros(max(4, tot), dtype=np.float32)
-        for a, o, n in zip(arrays, offs, ns):
-            host[o:o + n] = a
-        return torch.from_numpy(host).to(device), offs
-    buf = torch.zeros(max(4, tot), device=device, dtype=torch.float32)
-    for a, o, n in zip(arrays, offs, ns):
-        buf[o:o + n] = torch.as_tensor(a).to(device, torch.float32).view(-1)
-    return buf, offs
-
-
 def resample_batch(wavs: Sequence, srs: Sequence[int], sr_new: int = SAMPLE_RATE, resampler: Resampler = None,
                    device="cuda") -> list:
     """librosa.resample(wav, sr, sr_new) (resampy kaiser_best, fix=True) of every utterance, one launch for all: list of
     1-D device fp32 tensors of ceil(n * sr_new / sr) samples.  An utterance already at sr_new is returned unchanged (moved
     to the device, no launch)."""
-    torch = _dev()[0]
     r = resampler or Resampler(device, sr_new)
     if len(wavs) != len(srs):
         raise ValueError("resample_batch: one rate per waveform")
@@ -323,8 +294,7 @@ def resample_batch(wavs: Sequence, srs: Sequence[int], sr_new: int = SAMPLE_RATE
         else:
             todo.append(i)
     if todo:
-        arrs = [np.asarray(wavs[i], dtype=np.float32).ravel() if not torch.is_tensor(wavs[i]) else wavs[i].view(-1)
-                for i in todo]
+        arrs = [flat(wavs[i]) for i in todo]
         x, _ = pack(arrs, r.device)
         y, table = r.packed(x, [a.shape[0] for a in arrs], [int(srs[i]) for i in todo])
         for j, i in enumerate(todo):
@@ -334,7 +304,6 @@ def resample_batch(wavs: Sequence, srs: Sequence[int], sr_new: int = SAMPLE_RATE
 
 def volume_prepare(table, device) -> dict:
     """the host side of dvae_volume_normalize: the DVAE_VOLUME_TILE tile map of `table`'s segments, on the device"""
-    torch = _dev()[0]
     nseg = len(table)
     ntile = -(-table[:, 3] // VOLUME_TILE)
     tile_first = np.concatenate([[0], np.cumsum(ntile)]).astype(np.int64)
@@ -343,8 +312,8 @@ def volume_prepare(table, device) -> dict:
         a, b = tile_first[s], tile_first[s + 1]
         tiles[a:b, 0] = s
         tiles[a:b, 1] = np.arange(b - a, dtype=np.int64) * VOLUME_TILE
-    to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    return dict(nseg=nseg, ntiles=len(tiles), segs=to(table.astype(np.int64)), tiles=to(tiles), first=to(tile_first),
+    to = lambda a: upload(a, device, np.int64)
+    return dict(nseg=nseg, ntiles=len(tiles), segs=to(table), tiles=to(tiles), first=to(tile_first),
                 part=torch.empty(len(tiles), device=device, dtype=torch.float64),
                 ms=torch.empty(nseg, device=device, dtype=torch.float64),
                 gain=torch.empty(nseg, device=device, dtype=torch.float32),
@@ -353,7 +322,6 @@ def volume_prepare(table, device) -> dict:
 
 def volume_launch(y, prep: dict, target_dbfs=-30.0, increase_only=True):
     """dvae_volume_normalize alone (three launches, no sync); results stay in prep["ms" | "gain" | "silent"]"""
-    _, check, lib, ptr, stream = _dev()
     check(lib().dvae_volume_normalize(ptr(y), ptr(prep["segs"]), prep["nseg"], ptr(prep["tiles"]), prep["ntiles"],
                                       ptr(prep["first"]), ptr(prep["part"]), float(target_dbfs), int(bool(increase_only)),
                                       ptr(prep["ms"]), ptr(prep["gain"]), ptr(prep["silent"]), stream()),
@@ -371,8 +339,7 @@ def volume_packed(y, table, target_dbfs=-30.0, increase_only=True):
 def normalize_volume_batch(wavs: Sequence, target_dbfs=-30.0, increase_only=True, device="cuda"):
     """normalize_volume(wav, target_dbfs, increase_only) of every utterance, one pass for all -> (list of 1-D device fp32
     tensors, silent mask [n] bool numpy).  A silent (all-zero) utterance comes back unchanged and flagged."""
-    torch = _dev()[0]
-    arrs = [np.asarray(w, dtype=np.float32).ravel() if not torch.is_tensor(w) else w.view(-1) for w in wavs]
+    arrs = [flat(w) for w in wavs]
     if not arrs or any(a.shape[0] < 1 for a in arrs):
         raise ValueError("normalize_volume_batch: empty waveform")
     y, offs = pack(arrs, device)
@@ -526,7 +493,6 @@ def _save(path, mel):
 
 
 def _gpu_runner():
-    from .frontend import MelFrontend
     fe, rs = MelFrontend(), Resampler()
     return lambda wavs, srs: _run_batch(fe, rs, wavs, srs)
 
@@ -539,7 +505,7 @@ def _run_batch(fe, rs: Resampler, wavs, srs):
     keep = [i for i in range(len(wavs)) if not silent[i]]
     out = [(None, "silent")] * len(wavs)
     if keep:
-        packed, ms = fe._mel_packed(y, table[keep, 2], table[keep, 3])
+        packed, ms = fe.mel_packed(y, table[keep, 2], table[keep, 3])
         for i, m in zip(keep, fe.unpack(packed.cpu().numpy(), ms)):
             out[i] = (m, None)
     return out

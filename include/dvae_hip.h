@@ -501,9 +501,10 @@ int dvae_ola_gather(const float* y, const int64_t* segs, int nseg, int64_t rows,
  *   ms = sum over its tiles tile_first[s] .. tile_first[s+1] in order / n_out, gain = 10^((target - 10 log10 ms) / 20)
  *   (1 where increase_only and the change is < 0), y *= gain.  ms == 0: silent[s] = 1, gain 1 (the reference would
  *   write 0 * inf = NaN).  tiles from dvae_resample_segment_table with tile = DVAE_VOLUME_TILE; ms_out optional.
- * dvae_stft_frames_seg / dvae_mel_db_normalize_seg: dvae_stft_frames / dvae_mel_db_normalize on a packed batch, bit for
- *   bit, with the dvae_gl_segment_table layout {row0, M, sample0, n} in device memory: frame rows of segment s are
- *   [row0, row0 + M) of signal wav[sample0, sample0 + n); its [n_mels, M] block of `out` starts at n_mels * row0. */
+ * dvae_stft_frames_seg / dvae_mel_db_normalize_seg: dvae_stft_frames / dvae_mel_db_normalize on a packed batch (the same
+ *   kernels: one utterance is one segment passed by value), with the dvae_gl_segment_table layout {row0, M, sample0, n}
+ *   in device memory: frame rows of segment s are [row0, row0 + M) of signal wav[sample0, sample0 + n); its [n_mels, M]
+ *   block of `out` starts at n_mels * row0. */
 #define DVAE_RESAMPLE_TILE 256
 #define DVAE_VOLUME_TILE 2048
 int dvae_resample_segment_table(const int64_t* n_in, const int* filt, int nseg, const int64_t* filters, int nfilt,

@@ -14,6 +14,7 @@ import torch
 
 import dvae_amd  # noqa: F401
 from dvae_amd.frontend import MelFrontend, MelInverter
+from dvae_amd.packed import pinned_gemm
 
 
 def timed(fn, reps):
@@ -45,7 +46,7 @@ def main(n_utt=64, seconds=4.0, n_iter=32, reps=5):
     X = torch.randn(rows, 2 * inv.nbp, device="cuda")
     y = torch.empty(rows, inv.fsize, device="cuda")
     R = torch.empty(rows, 2 * inv.nbp, device="cuda")
-    gemm_ms = timed(lambda: (inv._gemm(X, inv.inv_basis, y, 2 * inv.nbp), inv._gemm(y, inv.dft_basis, R, inv.fsize)), 20)
+    gemm_ms = timed(lambda: (pinned_gemm(X, inv.inv_basis, y, 2 * inv.nbp), pinned_gemm(y, inv.dft_basis, R, inv.fsize)), 20)
     flop_iter = 2.0 * rows * inv.fsize * (2 * inv.nbp) * 2
     mel0 = mels[0].cpu().numpy().astype(np.float64)
     t0 = time.perf_counter()

@@ -51,12 +51,12 @@ def gpu_batch(sr, n_utt=64, seconds=4.0, reps=5):
     vprep = volume_prepare(table, y.device)
     copy_ms = timed(lambda: y.copy_(y0), reps)
     volume_kernel_ms = timed(lambda: (y.copy_(y0), volume_launch(y, vprep)), reps) - copy_ms
-    mel_call_ms = timed(lambda: fe._mel_packed(y0, table[:, 2], table[:, 3]), reps)
+    mel_call_ms = timed(lambda: fe.mel_packed(y0, table[:, 2], table[:, 3]), reps)
 
     def whole():
         yy, tt = r.packed(x, lens, srs)
         volume_packed(yy, tt)
-        fe._mel_packed(yy, tt[:, 2], tt[:, 3])
+        fe.mel_packed(yy, tt[:, 2], tt[:, 3])
     call_ms = timed(whole, reps)
     taps = r._rows[r._ids[sr]][2]
     fma = float(table[:, 4].sum()) * taps

@@ -102,11 +102,10 @@ def test_segmented_frames_and_db_equal_the_per_utterance_kernels():
     ns = [1, 255, 256, 4097, 16000 + 5]
     sigs = [torch.from_numpy(rs.uniform(-1, 1, n).astype(np.float32)).cuda() for n in ns]
     ms = [fe.num_frames(n) for n in ns]
+    from dvae_amd.packed import segment_table
     from dvae_amd.preprocess import pack
     wav, offs = pack(sigs)
-    table = np.zeros((len(ns), 4), dtype=np.int64)
-    table[:, 0] = np.concatenate([[0], np.cumsum(ms)[:-1]])
-    table[:, 1], table[:, 2], table[:, 3] = ms, offs, ns
+    table = segment_table(ms, offs, ns)
     segs = torch.from_numpy(table).cuda()
     rows = sum(ms)
     seg = torch.empty((rows, fe.fsize), device="cuda")
