@@ -541,11 +541,19 @@ __device__ __forceinline__ double dist_row(const float* __restrict__ p, const fl
   return sqrt(acc);
 }
 
+//
+// F0 (dvae_dtw_batch_f0): one more quantity rides along the same path the way the length does, the sum over the path's
+// cells of (lfx[i] - lfy[j])^2 with lfx / lfy the per-row log-F0 (indexed like x / y).  The difference and its square are
+// float64, the running sum is fp32 (ps: 32 KiB more LDS, 128 of the 160 KiB; a float64 payload would sit exactly at the
+// limit), so it never enters a comparison: cost and length are the F0 = false kernel's bits.
+template <bool F0>
 __global__ void __launch_bounds__(DTW_THREADS) dtw_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                           const int64_t* __restrict__ pairs, double* __restrict__ cost,
-                                                          int64_t* __restrict__ length) {
+                                                          int64_t* __restrict__ length, const float* __restrict__ lfx,
+                                                          const float* __restrict__ lfy, double* __restrict__ sse) {
   __shared__ double cs[2][DTW_MAX_SHORT];
   __shared__ int ls[2][DTW_MAX_SHORT];
+  __shared__ float ps[2][F0 ? DTW_MAX_SHORT : 1];
   const int tid = threadIdx.x;
   const int64_t* pr = pairs + 4 * blockIdx.x;
   const int64_t nx = pr[1], ny = pr[3];
@@ -553,6 +561,7 @@ __global__ void __launch_bounds__(DTW_THREADS) dtw_kernel(const float* __restric
     if (tid == 0) {
       cost[blockIdx.x] = __builtin_nan("");
       length[blockIdx.x] = 0;
+      if constexpr (F0) sse[blockIdx.x] = __builtin_nan("");
     }
     return;
   }
@@ -561,14 +570,18 @@ __global__ void __launch_bounds__(DTW_THREADS) dtw_kernel(const float* __restric
   const float* __restrict__ B = swap ? x + pr[0] * MCD_DIM : y + pr[2] * MCD_DIM;
   const int na = (int)(swap ? ny : nx);
   const int64_t nb = swap ? nx : ny;
+  const float* __restrict__ LA = F0 ? (swap ? lfy + pr[2] : lfx + pr[0]) : nullptr;
+  const float* __restrict__ LB = F0 ? (swap ? lfx + pr[0] : lfy + pr[2]) : nullptr;
   const int S = (na + DTW_THREADS - 1) / DTW_THREADS;
   const double inf = __builtin_inf();
   double cl[DTW_SLOTS], cu[DTW_SLOTS];              // own cell of the previous diagonal; last diagonal's (a-1) read
   int ll[DTW_SLOTS], lu[DTW_SLOTS];
+  float pl[F0 ? DTW_SLOTS : 1], pu[F0 ? DTW_SLOTS : 1];   // the payload of the same two cells
 #pragma unroll
   for (int s = 0; s < DTW_SLOTS; ++s) {
     cl[s] = cu[s] = inf;
     ll[s] = lu[s] = 0;
+    if constexpr (F0) pl[s] = pu[s] = 0.f;
   }
   const int64_t ndiag = (int64_t)na + nb - 1;
   for (int64_t dg = 0; dg < ndiag; ++dg) {
@@ -581,35 +594,55 @@ __global__ void __launch_bounds__(DTW_THREADS) dtw_kernel(const float* __restric
         const double d = dist_row(A + (int64_t)a * MCD_DIM, B + b * MCD_DIM);
         double c = d;
         int l = 1;
+        float e = 0.f, pp = 0.f;
+        if constexpr (F0) {
+          const double t = (double)LA[a] - (double)LB[b];
+          e = (float)(t * t);
+          pp = e;
+        }
         if (a > 0 || b > 0) {
           double cup = inf, clf = b > 0 ? cl[s] : inf, cdg = (a > 0 && b > 0) ? cu[s] : inf;
           int lup = 0;
+          float pup = 0.f;
           if (a > 0) {
             cup = cs[cur ^ 1][a - 1];
             lup = ls[cur ^ 1][a - 1];
+            if constexpr (F0) pup = ps[cur ^ 1][a - 1];
           }
           // order (i-1, j), (i, j-1), (i-1, j-1): (a-1, b), (a, b-1) when a = i; (a, b-1), (a-1, b) when a = j
           double bc = swap ? clf : cup;
           int bl = swap ? ll[s] : lup;
           const double c2 = swap ? cup : clf;
           const int l2 = swap ? lup : ll[s];
+          float bp = 0.f;
+          if constexpr (F0) bp = swap ? pl[s] : pup;
           if (c2 < bc) {
             bc = c2;
             bl = l2;
+            if constexpr (F0) bp = swap ? pup : pl[s];
           }
           if (cdg < bc) {
             bc = cdg;
             bl = lu[s];
+            if constexpr (F0) bp = pu[s];
           }
           c = d + bc;
           l = bl + 1;
           cu[s] = cup;
           lu[s] = lup;
+          if constexpr (F0) {
+            pp = bp + e;
+            pu[s] = pup;
+          }
         }
         cs[cur][a] = c;
         ls[cur][a] = l;
         cl[s] = c;
         ll[s] = l;
+        if constexpr (F0) {
+          ps[cur][a] = pp;
+          pl[s] = pp;
+        }
       }
     }
     __syncthreads();
@@ -621,7 +654,146 @@ __global__ void __launch_bounds__(DTW_THREADS) dtw_kernel(const float* __restric
       if (s == last / DTW_THREADS) {
         cost[blockIdx.x] = cl[s];
         length[blockIdx.x] = ll[s];
+        if constexpr (F0) sse[blockIdx.x] = (double)pl[s];
       }
+    }
+  }
+}
+
+// ---- F0 contour (evaluate.py; replaces pyworld.harvest of preprocessing/WORLD_processing.py:29-38): a
+// Viterbi pass over the F0_STATES lags of the voicing autocorrelation, every maximal run of voiced frames on its own.
+// One workgroup per utterance {row0, M, ..}; thread j < F0_STATES owns state j (lag lag_min + j).
+//   s_k(j) = (double)r[k][1+j] * (double)gain[1+j] / (double)r[k][0] - oct[j]
+//   D_k(j) = s_k(j) + max_i (D_{k-1}(i) - jump * |l2[j] - l2[i]|), the first maximal i on a tie; D = s at a run's first frame
+// in float64 with contraction off (every operation rounds once, in the order written, as a numpy restatement does).  The
+// previous frame's D (double-buffered) and l2 sit in LDS and are read as broadcasts: one barrier per frame.  The
+// back-pointers, one byte per state, go to back[rows][F0_LD]; at a run's last frame the first arg-max of D starts the
+// traceback, which reads them back F0_CHUNK frames at a time into LDS (coalesced), walks the chunk there (thread 0) and
+// lets one thread per frame write lag, f0 (parabolic refinement of r * gain around the lag) and, at the frame's rank among
+// the utterance's voiced frames (the row of feats that dvae_voicing_compact gave it), lf0v = ln f0.  No atomics, one
+// writer per element, and a launch reads only its own utterance.
+constexpr int F0_THREADS = 256, F0_STATES = 206, F0_LD = 208, F0_CHUNK = 256;
+static_assert(F0_LD <= F0_THREADS && F0_STATES <= 256 && (F0_LD & 7) == 0 && F0_LD >= F0_STATES, "one byte per state");
+
+__global__ void __launch_bounds__(F0_THREADS) f0_viterbi_kernel(const float* __restrict__ r, int ldr,
+                                                                const float* __restrict__ gain,
+                                                                const int* __restrict__ voiced,
+                                                                const int64_t* __restrict__ segs,
+                                                                const double* __restrict__ l2g,
+                                                                const double* __restrict__ octg, double jump, double rate,
+                                                                int lag_min, unsigned char* back, int* __restrict__ lag,
+                                                                float* __restrict__ f0, float* __restrict__ lf0v) {
+#pragma clang fp contract(off)
+  __shared__ double Ds[2][F0_LD];
+  __shared__ double l2s[F0_LD];
+  __shared__ unsigned int bps[F0_CHUNK * F0_LD / 4];
+  __shared__ int path[F0_CHUNK];
+  const int tid = threadIdx.x;
+  const bool own = tid < F0_STATES;
+  const int j = own ? tid : F0_STATES - 1;          // the idle threads shadow the last state and write nothing
+  const int64_t row0 = segs[4 * blockIdx.x], M = segs[4 * blockIdx.x + 1];
+  const double l2j = l2g[j], octj = octg[j], gj = (double)gain[1 + j];
+  if (tid < F0_LD) {
+    l2s[tid] = own ? l2j : 0.0;
+    if (!own) Ds[0][tid] = Ds[1][tid] = -__builtin_inf();
+  }
+  __syncthreads();
+  const unsigned char* bpb = reinterpret_cast<const unsigned char*>(bps);
+  int cur = 0, state = 0;
+  int64_t run0 = -1, vbase = 0;                     // first frame of the open run; voiced frames before it
+  int v_n = 0;
+  float r_n = 0.f, r0_n = 1.f;
+  if (M > 0) {
+    v_n = voiced[row0];
+    r_n = r[row0 * ldr + 1 + j];
+    r0_n = r[row0 * ldr];
+  }
+  for (int64_t k = 0; k < M; ++k) {
+    const int v = __builtin_amdgcn_readfirstlane(v_n);
+    const float rk = r_n, r0k = r0_n;
+    if (k + 1 < M) {                                // the next frame's loads fly under this frame's recurrence
+      v_n = voiced[row0 + k + 1];
+      r_n = r[(row0 + k + 1) * ldr + 1 + j];
+      r0_n = r[(row0 + k + 1) * ldr];
+    }
+    if (v) {
+      const double s = (double)rk * gj / (double)r0k - octj;
+      double d = s;
+      if (run0 < 0) {
+        run0 = k;
+      } else {
+        const double* Dp = Ds[cur ^ 1];
+        double best = -__builtin_inf();             // the pad states F0_STATES .. F0_LD-1 hold D = -inf and never win
+        int bi = 0;
+#pragma unroll 8
+        for (int i = 0; i < F0_LD; ++i) {
+          const double c = Dp[i] - jump * fabs(l2j - l2s[i]);
+          const bool g = c > best;
+          best = g ? c : best;
+          bi = g ? i : bi;
+        }
+        d = s + best;
+        if (own) back[(row0 + k) * F0_LD + j] = (unsigned char)bi;
+      }
+      if (own) Ds[cur][j] = d;
+      cur ^= 1;
+      __syncthreads();
+    } else if (tid == 0) {
+      lag[row0 + k] = 0;
+      f0[row0 + k] = 0.f;
+    }
+    if (run0 >= 0 && (!v || k + 1 == M)) {          // the run run0 .. e is complete; its last D is Ds[cur ^ 1]
+      const int64_t e = v ? k : k - 1;
+      if (tid == 0) {
+        const double* Df = Ds[cur ^ 1];
+        double bm = Df[0];
+        state = 0;
+        for (int i = 1; i < F0_STATES; ++i) {
+          if (Df[i] > bm) {
+            bm = Df[i];
+            state = i;
+          }
+        }
+      }
+      for (int64_t c1 = e; c1 >= run0; c1 -= F0_CHUNK) {
+        const int64_t c0 = c1 - (F0_CHUNK - 1) > run0 ? c1 - (F0_CHUNK - 1) : run0;
+        const int nf = (int)(c1 - c0 + 1);
+        const unsigned int* src = reinterpret_cast<const unsigned int*>(back + (row0 + c0) * F0_LD);
+        for (int w = tid; w < nf * (F0_LD / 4); w += F0_THREADS) bps[w] = src[w];
+        __syncthreads();
+        if (tid == 0) {
+          for (int f = nf - 1; f >= 0; --f) {
+            path[f] = state;
+            if (c0 + f > run0) {                    // the run's first frame has no predecessor (its row of back is unwritten)
+              const int p = bpb[f * F0_LD + state];
+              state = p < F0_STATES ? p : F0_STATES - 1;
+            }
+          }
+        }
+        __syncthreads();
+        if (tid < nf) {
+          const int64_t fr = c0 + tid;
+          const int st = path[tid];
+          const float* rr = r + (row0 + fr) * ldr;
+          double delta = 0.0;
+          if (st > 0 && st < F0_STATES - 1) {
+            const double qm = (double)rr[st] * (double)gain[st], q0 = (double)rr[1 + st] * (double)gain[1 + st],
+                         qp = (double)rr[2 + st] * (double)gain[2 + st];
+            const double den = qm - 2.0 * q0 + qp;
+            if (den < 0.0) {
+              delta = 0.5 * (qm - qp) / den;
+              delta = delta > 0.5 ? 0.5 : (delta < -0.5 ? -0.5 : delta);
+            }
+          }
+          const float fz = (float)(rate / ((double)(lag_min + st) + delta));
+          lag[row0 + fr] = lag_min + st;
+          f0[row0 + fr] = fz;
+          lf0v[row0 + vbase + (fr - run0)] = (float)log((double)fz);
+        }
+        __syncthreads();                            // bps / path are rewritten by the next chunk
+      }
+      vbase += e - run0 + 1;
+      run0 = -1;
     }
   }
 }
@@ -839,17 +1011,46 @@ DVAE_API int dvae_voicing_compact(const float* r, int ldr, int nlag, const float
   return dvae_check_launch();
 }
 
+// everything the DTW kernel relies on, from the host copy of the pair table, before any launch
+static bool dtw_refuses(const int64_t* pairs_host, int npairs) {
+  for (int p = 0; p < npairs; ++p) {
+    const int64_t* q = pairs_host + 4 * p;
+    if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0 || q[1] > ((int64_t)1 << 30) || q[3] > ((int64_t)1 << 30))
+      return true;
+    if (q[1] > 0 && q[3] > 0 && (q[1] < q[3] ? q[1] : q[3]) > DTW_MAX_SHORT) return true;
+  }
+  return false;
+}
+
 DVAE_API int dvae_dtw_batch(const float* x, const float* y, const int64_t* pairs, const int64_t* pairs_host, int npairs,
                             double* cost, int64_t* length, void* stream) {
   if (!x || !y || !pairs || !pairs_host || !cost || !length || npairs < 1 || ((((uintptr_t)x) | ((uintptr_t)y)) & 15))
     return DVAE_EINVAL;
-  for (int p = 0; p < npairs; ++p) {                // everything the kernel relies on, before any launch
-    const int64_t* q = pairs_host + 4 * p;
-    if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0 || q[1] > ((int64_t)1 << 30) || q[3] > ((int64_t)1 << 30))
-      return DVAE_EINVAL;
-    if (q[1] > 0 && q[3] > 0 && (q[1] < q[3] ? q[1] : q[3]) > DTW_MAX_SHORT) return DVAE_EINVAL;
-  }
-  hipLaunchKernelGGL(dtw_kernel, dim3((unsigned)npairs), dim3(DTW_THREADS), 0, (hipStream_t)stream, x, y, pairs, cost,
-                     length);
+  if (dtw_refuses(pairs_host, npairs)) return DVAE_EINVAL;
+  hipLaunchKernelGGL(dtw_kernel<false>, dim3((unsigned)npairs), dim3(DTW_THREADS), 0, (hipStream_t)stream, x, y, pairs,
+                     cost, length, (const float*)nullptr, (const float*)nullptr, (double*)nullptr);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_dtw_batch_f0(const float* x, const float* y, const float* lf0x, const float* lf0y, const int64_t* pairs,
+                               const int64_t* pairs_host, int npairs, double* cost, int64_t* length, double* sse,
+                               void* stream) {
+  if (!x || !y || !lf0x || !lf0y || !pairs || !pairs_host || !cost || !length || !sse || npairs < 1 ||
+      ((((uintptr_t)x) | ((uintptr_t)y)) & 15))
+    return DVAE_EINVAL;
+  if (dtw_refuses(pairs_host, npairs)) return DVAE_EINVAL;
+  hipLaunchKernelGGL(dtw_kernel<true>, dim3((unsigned)npairs), dim3(DTW_THREADS), 0, (hipStream_t)stream, x, y, pairs,
+                     cost, length, lf0x, lf0y, sse);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_f0_viterbi(const float* r, int ldr, int nlag, const float* gain, const int* voiced, const int64_t* segs,
+                             int nseg, const double* l2, const double* oct, double jump_cost, double sample_rate,
+                             int lag_min, unsigned char* back, int* lag, float* f0, float* lf0v, void* stream) {
+  if (!r || !gain || !voiced || !segs || !l2 || !oct || !back || !lag || !f0 || !lf0v || nseg < 1 || nlag != F0_STATES ||
+      ldr < nlag + 1 || lag_min < 1 || !(jump_cost >= 0.0) || !(sample_rate > 0.0) || (((uintptr_t)back) & 3))
+    return DVAE_EINVAL;
+  hipLaunchKernelGGL(f0_viterbi_kernel, dim3((unsigned)nseg), dim3(F0_THREADS), 0, (hipStream_t)stream, r, ldr, gain,
+                     voiced, segs, l2, oct, jump_cost, sample_rate, lag_min, back, lag, f0, lf0v);
   return dvae_check_launch();
 }

@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 310
+#define DVAE_ABI_VERSION 311
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -549,6 +549,29 @@ int dvae_voicing_compact(const float* r, int ldr, int nlag, const float* gain, c
                          float* feats, int* count, void* stream);
 int dvae_dtw_batch(const float* x, const float* y, const int64_t* pairs, const int64_t* pairs_host, int npairs,
                    double* cost, int64_t* length, void* stream);
+
+/* ---- F0 contour and log-F0 error along the MCD alignment (python -m dvae_amd.evaluate --f0) ----
+ * dvae_f0_viterbi replaces `pyworld.harvest` of preprocessing/WORLD_processing.py:29-38 `world_decompose` (F0 per 5 ms
+ *   frame, 0 on unvoiced frames), whose log statistics are `logf0_statistics` (:178-185).  One workgroup per utterance of
+ *   `segs`; r, gain, voiced as dvae_voicing_compact reads / writes them, nlag == DVAE_F0_STATES.  Every maximal run of
+ *   voiced frames is tracked on its own by a Viterbi pass over the states j (lag lag_min + j) in float64 without fused
+ *   multiply-add: s_k(j) = r[k][1+j] * gain[1+j] / r[k][0] - oct[j]; D = s at the run's first frame, then
+ *   D_k(j) = s_k(j) + max_i (D_{k-1}(i) - jump_cost * |l2[j] - l2[i]|), the first maximal i on a tie; the first arg-max
+ *   of the last D starts the traceback.  l2, oct: [DVAE_F0_STATES] float64 device tables.  back[rows, DVAE_F0_BACK_LD]
+ *   bytes: scratch for the back-pointers (4-byte aligned).  lag[row] = lag_min + j (0 unvoiced); f0[row] =
+ *   sample_rate / (lag + delta), delta the parabolic vertex of r * gain around the lag (0 at the first and last state or
+ *   where the parabola is not concave, clamped to +-0.5), 0 unvoiced; lf0v[row0 + k] = ln f0 of the utterance's k-th voiced
+ *   frame, the row dvae_voicing_compact gives that frame in feats; rows past count[s] are not written.
+ * dvae_dtw_batch_f0 replaces nothing of its own: it is dvae_dtw_batch (the same kernel body, cost and length bit-identical,
+ *   the same refusals) that also carries, the way the path length is carried, the sum over the path's cells of
+ *   (lf0x[x_row0 + i] - lf0y[y_row0 + j])^2 -> sse[p] (float64 terms, fp32 running sum; NaN where cost is NaN). */
+#define DVAE_F0_STATES 206
+#define DVAE_F0_BACK_LD 208
+int dvae_f0_viterbi(const float* r, int ldr, int nlag, const float* gain, const int* voiced, const int64_t* segs, int nseg,
+                    const double* l2, const double* oct, double jump_cost, double sample_rate, int lag_min,
+                    unsigned char* back, int* lag, float* f0, float* lf0v, void* stream);
+int dvae_dtw_batch_f0(const float* x, const float* y, const float* lf0x, const float* lf0y, const int64_t* pairs,
+                      const int64_t* pairs_host, int npairs, double* cost, int64_t* length, double* sse, void* stream);
 
 /* ---- opt-in per-family kernel timing with HIP events on the launch stream (bench.py roofline) ----
  * family: 0 = off, 1 = GEMM/conv contraction kernel, 2 = LSTM step kernels.

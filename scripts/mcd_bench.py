@@ -2,7 +2,10 @@
 of varied pitch and noise level) the ms of the feature pass per call (both sides, 512 utterances, one packed batch; from
 host arrays, and from device tensors: the GPU passes without the host packing and upload), of the DTW kernel alone on
 prepared device tables, and of the whole mcd_batch per call (host packing, table uploads and read-backs included); and the
-float64 numpy restatement (tests/test_mcd.py: features of both sides + DTW) on one pair.  Prints one JSON line."""
+float64 numpy restatement (tests/test_mcd.py: features of both sides + DTW) on one pair.  Prints one JSON line.
+With --f0 the line also carries, measured in the same call: f0_viterbi_ms (the F0 tracker's launch for the
+512 utterances on the feature pass's buffers), dtw_f0_kernel_ms (the DTW kernel carrying the log-F0 payload, next to
+dtw_kernel_ms), mcd_batch_f0_ms (mcd_batch(f0=True) per call) and mean_lf0_rmse_cents."""
 import json
 import os
 import sys
@@ -32,7 +35,7 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
-def main(pairs=256, seconds=4.0, reps=5):
+def main(pairs=256, seconds=4.0, reps=5, f0=False):
     rs = np.random.RandomState(0)
     n = int(16000 * seconds)
     conv = [harmonic(n, float(rs.uniform(80, 300)), seed=2 * i, snr_db=float(rs.uniform(10, 30))) for i in range(pairs)]
@@ -61,14 +64,33 @@ def main(pairs=256, seconds=4.0, reps=5):
     c, l = dtw_ref(fx["mc"][fx["voiced"], :ev.DIM], fy["mc"][fy["voiced"], :ev.DIM])
     f64_one_pair_s = time.perf_counter() - t0
     cells = float(np.sum(count[:P].astype(np.float64) * count[P:]))
+    extra = {}
+    if f0:
+        rows = int(table[:, 1].sum())
+        segs = torch.from_numpy(np.ascontiguousarray(table, dtype=np.int64)).cuda()
+        bufs = fe.f0_viterbi(out["r"], out["voiced"], segs, 2 * P, rows)
+        f0_viterbi_ms = timed(lambda: fe.f0_viterbi(out["r"], out["voiced"], segs, 2 * P, rows, out=bufs), reps)
+        sse = torch.empty(P, device="cuda", dtype=torch.float64)
+        lf0v = bufs["lf0v"]
+
+        def dtw_f0():
+            rc = lib().dvae_dtw_batch_f0(ptr(feats), ptr(feats), ptr(lf0v), ptr(lf0v), ptr(tab_d), tab.ctypes.data, P,
+                                         ptr(cost), ptr(length), ptr(sse), stream())
+            assert rc == 0, rc
+        dtw_f0_kernel_ms = timed(dtw_f0, reps)
+        mcd_batch_f0_ms = timed(lambda: ev.mcd_batch(conv, ref, features=fe, f0=True), reps)
+        res_f0 = ev.mcd_batch(conv, ref, features=fe, f0=True)
+        extra = dict(f0_viterbi_ms=round(f0_viterbi_ms, 3), dtw_f0_kernel_ms=round(dtw_f0_kernel_ms, 3),
+                     mcd_batch_f0_ms=round(mcd_batch_f0_ms, 3),
+                     mean_lf0_rmse_cents=round(res_f0["mean_lf0_rmse_cents"], 3))
     print(json.dumps(dict(pairs=P, seconds=seconds, frames_per_utterance=int(table[0, 1]),
                           voiced_mean=float(count.mean()), dtw_cells=cells, features_ms=round(features_ms, 3),
                           features_device_ms=round(features_device_ms, 3),
                           dtw_kernel_ms=round(dtw_kernel_ms, 3), dtw_gcells_per_s=round(cells / dtw_kernel_ms / 1e6, 3),
                           mcd_batch_ms=round(mcd_batch_ms, 3), mean_mcd=round(res["mean_mcd"], 4),
                           f64_one_pair_s=round(f64_one_pair_s, 3), f64_one_pair_mcd=round(float(ev.mcd_from([c], [l])[0]), 4),
-                          gpu_one_pair_mcd=round(float(res["mcd"][0]), 4))))
+                          gpu_one_pair_mcd=round(float(res["mcd"][0]), 4), **extra)))
 
 
 if __name__ == "__main__":
-    main()
+    main(f0="--f0" in sys.argv[1:])
