@@ -61,7 +61,7 @@ COMPUTE_MODES = {"fp32": MODE_F32, "f32": MODE_F32, "float32": MODE_F32, "bf16":
                  "fp32x3": MODE_F32X3, "f32x3": MODE_F32X3}
 
 DEFAULT_COMPUTE_DTYPE = "fp32x3"
-ABI_VERSION = 311     # DVAE_ABI_VERSION of include/dvae_hip.h
+ABI_VERSION = 312     # DVAE_ABI_VERSION of include/dvae_hip.h
 
 # name -> (restype, argtypes); mirrors include/dvae_hip.h one to one
 SIGNATURES = {
@@ -155,6 +155,8 @@ SIGNATURES = {
     "dvae_dtw_batch": (i32, [vp, vp, vp, vp, i32, vp, vp, vp]),
     "dvae_f0_viterbi": (i32, [vp, i32, i32, vp, vp, vp, i32, vp, vp, C.c_double, C.c_double, i32, vp, vp, vp, vp, vp]),
     "dvae_dtw_batch_f0": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "dvae_softmax_ce": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, vp]),
+    "dvae_scale_by": (i32, [vp, vp, vp, i64, vp]),
     "dvae_prof_enable": (i32, [i32]),
     "dvae_prof_collect": (i32, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]),
     "dvae_prof_collect_tags": (i32, [C.POINTER(C.c_uint), C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double),

@@ -1502,6 +1502,68 @@ class LossGVAE2FullFn(torch.autograd.Function):
         return (None, None, *[grads[i] if need[i + 2] else None for i in range(6)], None, None, None, None, None)
 
 
+# ----------------------------------------------------------------------------- softmax cross-entropy (probe.py)
+CE_MAX_CLASSES = 1024     # DVAE_CE_MAX_CLASSES
+
+
+def _labels_ok(logits, labels):
+    _ok(logits)
+    if logits.dim() != 2:
+        raise ValueError(f"softmax cross-entropy needs logits [rows, ld], got {tuple(logits.shape)}")
+    if not (labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == logits.shape[0]):
+        raise ValueError("softmax cross-entropy needs one contiguous int32 GPU label per row of the logits")
+
+
+def softmax_ce(logits, labels, classes=None, grad_scale=1.0, dlogits=None, reduce=True):
+    """dvae_softmax_ce on logits [rows, ld] (classes <= ld, the columns behind are padding) and int32 labels [rows]
+    (negative: the row is ignored) -> (row_loss [rows], row_pred [rows] int32, out [4] or None).  dlogits: None (no
+    gradient), a tensor like logits, or logits itself (in place): grad_scale * (softmax - onehot), padding columns 0.
+    out = {loss sum, counted rows, correct rows, mean loss} over the counted rows."""
+    _labels_ok(logits, labels)
+    if dlogits is not None and dlogits is not logits:
+        _ok(dlogits)
+        if dlogits.shape != logits.shape:
+            raise ValueError("softmax cross-entropy: dlogits must have the shape of the logits")
+    rows, ld = logits.shape
+    classes = ld if classes is None else int(classes)
+    row_loss = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    row_pred = torch.empty(rows, device=logits.device, dtype=torch.int32)
+    out = torch.empty(4, device=logits.device, dtype=torch.float32) if reduce else None
+    check(lib().dvae_softmax_ce(ptr(logits), ptr(labels), ptr(dlogits), ptr(row_loss), ptr(row_pred), ptr(out), rows,
+                                classes, ld, float(grad_scale), stream()), "dvae_softmax_ce")
+    return row_loss, row_pred, out
+
+
+def softmax_ce_eval(logits, labels, classes=None):
+    """(loss_sum, counted, correct) of the counted rows as a device tensor [3] (fp32; no gradient, no host sync)."""
+    return softmax_ce(logits.detach(), labels, classes)[2][:3]
+
+
+class SoftmaxCeFn(torch.autograd.Function):
+    """F.cross_entropy(logits[:, :classes], labels, ignore_index=<any negative>) as ONE pass over the logits: the mean
+    loss over the counted rows (a device scalar), with the gradient of the logits left behind pre-scaled by 1 / count.
+    `count`: the number of rows with a label >= 0 — the labels come from the host, so the caller knows it without a
+    device synchronisation.  Backward multiplies the kept gradient by the incoming scalar (dvae_scale_by)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, classes, count):
+        if int(count) < 1:
+            raise ValueError("SoftmaxCeFn: no counted row")
+        dl = torch.empty_like(logits)
+        out = softmax_ce(logits, labels, classes, 1.0 / int(count), dl)[2]
+        ctx.save_for_backward(dl)
+        return out[3]
+
+    @staticmethod
+    def backward(ctx, g):
+        dl, = ctx.saved_tensors
+        g = g.contiguous()
+        _ok(g)
+        dx = torch.empty_like(dl)
+        check(lib().dvae_scale_by(ptr(dl), ptr(g), ptr(dx), dl.numel(), stream()), "dvae_scale_by")
+        return dx, None, None, None
+
+
 def prof_enable(family: int):
     check(lib().dvae_prof_enable(family), "dvae_prof_enable")
 

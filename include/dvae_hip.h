@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 311
+#define DVAE_ABI_VERSION 312
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -572,6 +572,27 @@ int dvae_f0_viterbi(const float* r, int ldr, int nlag, const float* gain, const 
                     unsigned char* back, int* lag, float* f0, float* lf0v, void* stream);
 int dvae_dtw_batch_f0(const float* x, const float* y, const float* lf0x, const float* lf0y, const int64_t* pairs,
                       const int64_t* pairs_host, int npairs, double* cost, int64_t* length, double* sse, void* stream);
+
+/* ---- speaker-identity probe of the latents (python -m dvae_amd.probe) ----
+ * dvae_softmax_ce replaces the loss of model/train_feature_selection.py:39-41 (`F.cross_entropy` on the classifier's
+ *   output; the reference applies a softmax first, model/feature_selection.py:41, which this does not repeat) and the
+ *   arg-max accuracy of :44-50.  logits [rows, ld] fp32, classes <= ld, ld % 4 == 0, classes <= DVAE_CE_MAX_CLASSES,
+ *   logits / dlogits 16-byte aligned; labels [rows] int32.  One wavefront per row, the row read once:
+ *     row_loss[r] = logsumexp(logits[r, :classes]) - logits[r, label]   (the row maximum subtracted first)
+ *     row_pred[r] = arg-max over [0, classes), the lowest index on a tie
+ *     dlogits[r, c] = grad_scale * (softmax - onehot) for c < classes, 0 for classes <= c < ld (the contractions behind
+ *                     read whole ld-wide rows).  May be null (evaluation); may be `logits` itself (in place).
+ *   A row whose label is negative (or >= classes) is IGNORED: row_loss 0, gradient row 0, not counted; row_pred is
+ *   still its arg-max.  out (optional, 4 floats, written by a second, one-workgroup launch that adds the rows in a fixed
+ *   order in float64): {sum of row_loss over the counted rows, counted rows, counted rows with row_pred == label,
+ *   out[0] / out[1] (0 when nothing is counted)}.  No atomics: a row's outputs do not depend on the rest of the batch and
+ *   two runs give the same bits.
+ * dvae_scale_by: y[i] = x[i] * scale[0], i < n (n % 4 == 0; scale a DEVICE scalar: the incoming gradient of the mean
+ *   loss in ops.SoftmaxCeFn.backward; y may be x). */
+#define DVAE_CE_MAX_CLASSES 1024
+int dvae_softmax_ce(const float* logits, const int* labels, float* dlogits, float* row_loss, int* row_pred, float* out,
+                    int rows, int classes, int64_t ld, float grad_scale, void* stream);
+int dvae_scale_by(const float* x, const float* scale, float* y, int64_t n, void* stream);
 
 /* ---- opt-in per-family kernel timing with HIP events on the launch stream (bench.py roofline) ----
  * family: 0 = off, 1 = GEMM/conv contraction kernel, 2 = LSTM step kernels.
