@@ -128,7 +128,12 @@ class FlatAdam:
         """Host -> device copy of (lr, grad_scale) when they changed since the last copy.  NOT capturable by design: the
         trainer calls it before capture / replay, `step()` calls it itself when the stream is not capturing."""
         lr = float(self.param_groups[0]["lr"])
-        gs = float(self._dev_scalars[1] if (grad_scale is None and self._dev_scalars) else (grad_scale or 1.0))
+        # None: whatever was last sent (1.0 before anything was).  0.0 is a scale like any other: the moments decay and the
+        # parameters move by the decayed first moment
+        if grad_scale is None:
+            gs = float(self._dev_scalars[1]) if self._dev_scalars else 1.0
+        else:
+            gs = float(grad_scale)
         if self._dev_scalars != (lr, gs):
             if self.dev_state.is_cuda:
                 # staged through a small ring of PINNED slots, asynchronously: a per-step schedule must not stall the host
@@ -188,7 +193,7 @@ class FlatAdam:
             ops.join_side()     # weight-gradient work may still be running on the side stream
             ops.fold_pending(self)      # the k-split slabs of this step's weight gradients: one table-driven launch, fixed order
             if torch.cuda.is_current_stream_capturing():
-                if self._dev_scalars is None or self._dev_scalars[1] != float(grad_scale):
+                if self._dev_scalars is None or (grad_scale is not None and self._dev_scalars[1] != float(grad_scale)):
                     raise RuntimeError("FlatAdam.step under capture: call sync_scalars(grad_scale) before the capture")
             else:
                 self.sync_scalars(grad_scale)

@@ -393,6 +393,31 @@ def test_store_first_counters_restart_with_zero_grad():
         opt._store_first_guard()
 
 
+def test_sync_scalars_honours_a_zero_grad_scale_and_none_keeps_the_last():
+    """grad_scale = 0.0 is a scale (it used to become 1.0 through `grad_scale or 1.0`); None means "whatever was last sent",
+    1.0 before anything was; a changed learning rate is sent along with the scale that is already there."""
+    from dvae_amd.optim import FlatAdam
+    opt = FlatAdam([("a", torch.nn.Parameter(torch.randn(8, 4)))], lr=1e-3)
+    sent = lambda: (float(opt.dev_state[4]), float(opt.dev_state[5]))
+    lr32 = float(torch.tensor(1e-3, dtype=torch.float32))
+    opt.sync_scalars()
+    assert sent() == (lr32, 1.0) and opt._dev_scalars == (1e-3, 1.0)
+    opt.sync_scalars(0.0)
+    assert sent() == (lr32, 0.0) and opt._dev_scalars == (1e-3, 0.0)
+    opt.sync_scalars(None)
+    assert sent() == (lr32, 0.0)
+    opt.param_groups[0]["lr"] = 0.5
+    opt.sync_scalars()
+    assert sent() == (0.5, 0.0)                          # the schedule moved, the scale stayed
+    opt.sync_scalars(0.25)
+    assert sent() == (0.5, 0.25)
+    opt.sync_scalars(None)
+    assert sent() == (0.5, 0.25)
+    opt.load_state_dict(opt.state_dict())                # a resume forgets what was sent: None is 1.0 again
+    opt.sync_scalars(None)
+    assert sent() == (0.5, 1.0)
+
+
 def test_shared_gpu_decision_needs_local_world_size(monkeypatch):
     """WORLD_SIZE counts the ranks of every node; only LOCAL_WORLD_SIZE may switch the persistent recurrences off."""
     import dvae_amd  # noqa: F401
