@@ -337,6 +337,9 @@ int bn_bwd_launch(const float* dZ, const float* Y, const void* Z, const float* m
   // without Z the activation's derivative is recomputed from Y: ReLU (a compare) or none — not tanh (a libm call per
   // element costs these HBM-bound passes more than the 4 bytes it saves)
   if (zre && (!beta || (act != DVAE_ACT_RELU && act != DVAE_ACT_NONE))) return DVAE_EINVAL;
+  // in place (dY == dZ) every thread overwrites the 16 bytes it has just read; a bf16 dY is half as wide, so quad i would
+  // land on the fp32 dZ of quad i/2, which another thread may not have read yet
+  if (dyb && dY == (const void*)dZ) return DVAE_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int ch = n_chunks(R);
   double* part = (double*)ws;

@@ -178,7 +178,9 @@ int dvae_conv_unpack_add_w(const float* dWp, float* dW, int Cout, int Cin, void*
  *   group order with `momentum` and the unbiased variance; *num_batches_tracked += G. running_* may be null.
  * dvae_bn_apply_fwd: Z = act((Y-mean)*rstd*gamma + beta) (+ residual if non-null)
  * dvae_bn_bwd: given dZ, saved Y and Z: dY (may alias dZ), dgamma += , dbeta += ; the residual branch's
- *   gradient is dZ itself (handled by the caller).
+ *   gradient is dZ itself (handled by the caller).  dY == dZ is allowed with an fp32 dY only: a bf16 dY (dtypes bit 1)
+ *   written over the fp32 dZ would overwrite quads that other threads have yet to read, so dvae_bn_bwd and
+ *   dvae_bn_bwd_from_y return DVAE_EINVAL for it and write nothing.  dgamma / dbeta may be null (not accumulated).
  */
 int64_t dvae_bn_ws_bytes(int R, int C, int G);
 int dvae_bn_stats_fwd(const float* Y, float* mean, float* rstd, float* running_mean, float* running_var,
