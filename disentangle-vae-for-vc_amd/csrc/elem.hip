@@ -307,9 +307,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // Device-resident step counter, bias corrections, learning rate and gradient scale, so that a captured hipGraph replays a
 // correct Adam step: state[0] = t (as float), state[1] = 1 - beta1^t, state[2] = sqrt(1 - beta2^t), state[4] = lr,
 // state[5] = grad_scale.  `skip`: while *skip != 0 (sticky error word of the persistent LSTM launches) nothing is touched.
-__global__ void adam_tick_kernel(float* __restrict__ state, float b1, float b2, const unsigned* __restrict__ skip) {
+// CLIP (dvae_adam_flat_dev_clip): clip[3] stands in for state[5], and while clip[4] != 0 (this step's gradient is not finite,
+// grad_clip_finalize_kernel) the step does not happen: no tick here, no write of p, m, v below
+template <bool CLIP>
+__global__ void adam_tick_kernel(float* __restrict__ state, float b1, float b2, const unsigned* __restrict__ skip,
+                                 const float* __restrict__ clip) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     if (skip && __hip_atomic_load(skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    if (CLIP && clip[4] != 0.f) return;
     const double t = (double)state[0] + 1.0;
     state[0] = (float)t;
     state[1] = (float)(1.0 - pow((double)b1, t));
@@ -320,15 +325,26 @@ struct AdamClear {
   int64_t lo[8], hi[8];
   int n;
 };
-template <int U>
+template <int U, bool CLIP>
 __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, float* __restrict__ g,
                                                        float* __restrict__ m, float* __restrict__ v, int64_t n4,
                                                        float b1, float b2, float eps, const float* __restrict__ state,
-                                                       const unsigned* __restrict__ skip, AdamClear clr) {
+                                                       const unsigned* __restrict__ skip, AdamClear clr,
+                                                       const float* __restrict__ clip) {
   if (skip && __hip_atomic_load(skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-  const float bc1 = state[1], bc2s = state[2], lr = state[4], gs = state[5];
-  const float step_size = lr / bc1;
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  if (CLIP && clip[4] != 0.f) {
+    // a gradient that is not finite: p, m, v keep their bits, but the clear ranges are still zeroed — the next backward
+    // pass accumulates into them (store-first gradients are overwritten by it anyway)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+      bool c = false;
+      for (int r = 0; r < clr.n; ++r) c |= (4 * i >= clr.lo[r]) & (4 * i < clr.hi[r]);
+      if (c) *reinterpret_cast<f32x4*>(g + 4 * i) = z;
+    }
+    return;
+  }
+  const float bc1 = state[1], bc2s = state[2], lr = state[4], gs = CLIP ? clip[3] : state[5];
+  const float step_size = lr / bc1;
   // U independent 16-byte accesses per tensor and thread per trip: 4 U loads in flight before the first use
   for (int64_t i0 = (int64_t)blockIdx.x * (256 * U) + threadIdx.x; i0 < n4; i0 += (int64_t)gridDim.x * (256 * U)) {
     f32x4 pp[U], gg[U], mm[U], vv[U];
@@ -360,6 +376,80 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, fl
       if (c) *reinterpret_cast<f32x4*>(g + 4 * i) = z;     // plain store: the next step's launches accumulate into it
     }
   }
+}
+
+// ------------------------------------------------------------------ gradient norm, clipping, non-finite guard
+// torch.nn.utils.clip_grad_norm_ over the whole flat gradient, on the device: sum of squares (one pass over g, float64) ->
+// finalize (norm, clip coefficient, the gradient scale Adam then reads, the non-finite flag) -> dvae_adam_flat_dev_clip.
+// The square of a finite float32 is exact in a double and n * FLT_MAX^2 ~ 1e85 cannot overflow one, so "the sum is not
+// finite" means exactly "some element is not finite": no flag pass.  No floating-point atomics: the grid and the order
+// of every addition depend on n alone, so the norm has the same bits run after run.
+constexpr int SUMSQ_U = 2;          // 16-byte loads in flight per thread and trip
+constexpr int SUMSQ_CAP = 2048;     // workgroups at most = float64 partial sums in the workspace
+inline int sumsq_blocks(int64_t n) {
+  const int64_t n4 = n >> 2;
+  int64_t b = (n4 + 256 * SUMSQ_U - 1) / (256 * SUMSQ_U);
+  if (b < 1) b = 1;
+  return (int)(b > SUMSQ_CAP ? SUMSQ_CAP : b);
+}
+
+template <int U>
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, double* __restrict__ part,
+                                                         int64_t n4) {
+  double acc = 0.0;
+  for (int64_t i0 = (int64_t)blockIdx.x * (256 * U) + threadIdx.x; i0 < n4; i0 += (int64_t)gridDim.x * (256 * U)) {
+    f32x4 gg[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * 256 < n4 ? i0 + u * 256 : i0;      // clamped like adam_dev_kernel's: the tail is not added
+      gg[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + 4 * i));      // streamed once
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (i0 + u * 256 >= n4) break;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc += (double)gg[u][k] * (double)gg[u][k];      // the product is exact
+    }
+  }
+  acc = wave_sum_d(acc);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// One workgroup.  clip: float[8]
+//   [0] max_norm (host-written; +inf: measure and guard, never clip)   [1] norm   [2] coef   [3] eff = grad_scale * coef
+//   [4] 1 while this step is to be skipped (gradient not finite and `guard`)   [5] skipped steps   [6] clipped steps
+//   [7] 1 when this step's gradient is not finite, guarded or not
+// float64 throughout, rounded once on each store.
+__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* __restrict__ part, int nparts,
+                                                                 const float* __restrict__ state,
+                                                                 float* __restrict__ clip,
+                                                                 const unsigned* __restrict__ skip, int guard) {
+  if (skip && __hip_atomic_load(skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  // thread t adds the partials t, t + 256, ... in index order, then the waves' butterflies, then the four waves in order
+  double a = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) a += part[i];
+  a = wave_sum_d(a);
+  __shared__ double red[4];
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const double sum = (red[0] + red[1]) + (red[2] + red[3]);
+  const double gs = (double)state[5], max_norm = (double)clip[0];
+  const bool bad = !(sum <= 1.7976931348623157e308);      // +inf or NaN
+  const double norm = gs * sqrt(sum);                     // of the gradient Adam consumes (the average over ranks)
+  const double ratio = max_norm / (norm + 1e-6);          // clip_grad_norm_, its 1e-6 included
+  const double coef = ratio < 1.0 ? ratio : 1.0;          // a NaN ratio does not clip
+  const bool skipped = bad && guard;
+  clip[1] = (float)norm;                                  // above FLT_MAX: +inf, while eff below comes from the double
+  clip[2] = (float)coef;
+  clip[3] = (float)(gs * coef);                           // coef == 1: grad_scale, bit for bit
+  clip[4] = skipped ? 1.f : 0.f;
+  clip[7] = bad ? 1.f : 0.f;
+  if (skipped) clip[5] += 1.f;
+  else if (coef < 1.0) clip[6] += 1.f;
 }
 
 // ------------------------------------------------------------------ layout
@@ -724,9 +814,9 @@ DVAE_API int dvae_adam_flat(float* p, const float* g, float* m, float* v, int64_
   return dvae_check_launch();
 }
 
-DVAE_API int dvae_adam_flat_dev(float* p, float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
+static int adam_flat_dev_launch(float* p, float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
                                 float* state, const unsigned* skip_if_nonzero, const dvae_ranges_t* clear, int tick,
-                                void* stream) {
+                                const float* clip, void* stream) {
   if (!p || !g || !m || !v || !state || n < 4 || (n & 3)) return DVAE_EINVAL;
   if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return DVAE_EINVAL;
   AdamClear c{};
@@ -741,14 +831,55 @@ DVAE_API int dvae_adam_flat_dev(float* p, float* g, float* m, float* v, int64_t 
     }
   }
   hipStream_t s = (hipStream_t)stream;
-  if (tick) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, s, state, beta1, beta2, skip_if_nonzero);
 #ifndef DVAE_ADAM_U
 #define DVAE_ADAM_U 2
 #endif
   constexpr int U = DVAE_ADAM_U;
   const int64_t n4 = n >> 2;
-  hipLaunchKernelGGL(adam_dev_kernel<U>, dim3(nblk((n4 + U - 1) / U, 256, 2048)), dim3(256), 0, s, p, g, m, v, n4, beta1,
-                     beta2, eps, state, skip_if_nonzero, c);
+  const dim3 grid(nblk((n4 + U - 1) / U, 256, 2048));
+  if (clip) {
+    if (tick) hipLaunchKernelGGL(adam_tick_kernel<true>, dim3(1), dim3(64), 0, s, state, beta1, beta2, skip_if_nonzero, clip);
+    hipLaunchKernelGGL((adam_dev_kernel<U, true>), grid, dim3(256), 0, s, p, g, m, v, n4, beta1, beta2, eps, state,
+                       skip_if_nonzero, c, clip);
+  } else {
+    if (tick) hipLaunchKernelGGL(adam_tick_kernel<false>, dim3(1), dim3(64), 0, s, state, beta1, beta2, skip_if_nonzero, clip);
+    hipLaunchKernelGGL((adam_dev_kernel<U, false>), grid, dim3(256), 0, s, p, g, m, v, n4, beta1, beta2, eps, state,
+                       skip_if_nonzero, c, clip);
+  }
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_adam_flat_dev(float* p, float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
+                                float* state, const unsigned* skip_if_nonzero, const dvae_ranges_t* clear, int tick,
+                                void* stream) {
+  return adam_flat_dev_launch(p, g, m, v, n, beta1, beta2, eps, state, skip_if_nonzero, clear, tick, nullptr, stream);
+}
+
+DVAE_API int dvae_adam_flat_dev_clip(float* p, float* g, float* m, float* v, int64_t n, float beta1, float beta2,
+                                     float eps, float* state, const unsigned* skip_if_nonzero,
+                                     const dvae_ranges_t* clear, int tick, const float* clip, void* stream) {
+  if (!clip) return DVAE_EINVAL;
+  return adam_flat_dev_launch(p, g, m, v, n, beta1, beta2, eps, state, skip_if_nonzero, clear, tick, clip, stream);
+}
+
+DVAE_API int64_t dvae_grad_sumsq_ws_bytes(int64_t n) {
+  if (n < 4 || (n & 3)) return 0;
+  return (int64_t)sumsq_blocks(n) * sizeof(double);
+}
+
+DVAE_API int dvae_grad_sumsq(const float* g, int64_t n, void* ws, void* stream) {
+  if (!g || !ws || n < 4 || (n & 3) || (((uintptr_t)g) & 15) || (((uintptr_t)ws) & 7)) return DVAE_EINVAL;
+  hipLaunchKernelGGL(grad_sumsq_kernel<SUMSQ_U>, dim3(sumsq_blocks(n)), dim3(256), 0, (hipStream_t)stream, g,
+                     reinterpret_cast<double*>(ws), n >> 2);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_grad_clip_finalize(const void* ws, int64_t n, const float* state, float* clip,
+                                     const unsigned* skip_if_nonzero, int guard_nonfinite, void* stream) {
+  if (!ws || !state || !clip || n < 4 || (n & 3) || (((uintptr_t)ws) & 7)) return DVAE_EINVAL;
+  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const double*>(ws), sumsq_blocks(n), state, clip, skip_if_nonzero,
+                     guard_nonfinite ? 1 : 0);
   return dvae_check_launch();
 }
 

@@ -25,6 +25,15 @@ import torch.distributed as dist
 from . import ops
 
 
+def refuse_sharded_clip(optimizer):
+    """A sharded step (mode "rs_ag") sees only this rank's slices of the reduced gradient: its norm would need a sum of the
+    ranks' sums of squares first, which is not built.  Clipping by a shard's norm would scale every rank differently."""
+    if getattr(optimizer, "max_norm", None) is not None:
+        raise ValueError("gradient clipping (FlatAdam.set_grad_clip) with a sharded optimizer step (GradReducer mode 'rs_ag') "
+                         "is not supported: the global norm needs a cross-rank sum; use mode 'all_reduce' or "
+                         "set_grad_clip(None)")
+
+
 class GradReducer:
     """mode "all_reduce" (default): every bucket is summed over the ranks in place (dist.all_reduce) and every rank
     runs the full Adam launch over all parameters.
@@ -177,8 +186,9 @@ class GradReducer:
         soon as its slice is updated.  In "all_reduce" mode this is the plain full step."""
         scale = 1.0 / self.world_size
         if self.mode != "rs_ag":
-            optimizer.step(grad_scale=scale)
+            optimizer.step(grad_scale=scale)      # every rank holds the whole reduced gradient: one norm, the same everywhere
             return
+        refuse_sharded_clip(optimizer)
         flat_p = optimizer.flat_p
         works = []
         for b, (lo, hi) in enumerate(self.buckets):

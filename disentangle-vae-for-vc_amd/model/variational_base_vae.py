@@ -63,13 +63,16 @@ class VariationalBaseModelVAE:
 
     # ---- data parallel (new functionality: the reference is single-device)
     def attach_reducer(self, reducer):
+        sharded = reducer is not None and getattr(reducer, "mode", "all_reduce") == "rs_ag"
+        if sharded and self.optimizer is not None:
+            from ..ddp import refuse_sharded_clip
+            refuse_sharded_clip(self.optimizer)     # ValueError, and nothing attached: a shard's norm is not the gradient's
         self.reducer = reducer
         if self.optimizer is not None:
             # a sharded step (rs_ag) reads — and could clear — only this rank's slices of the gradient buffer: zero_grad
             # launches every step while such a reducer is attached; whatever the setting was before comes back with the
             # next reducer that is not sharded (or with None), so switching modes back and forth leaves no trace
             opt = self.optimizer
-            sharded = reducer is not None and getattr(reducer, "mode", "all_reduce") == "rs_ag"
             if sharded:
                 if getattr(self, "_fold_before_shard", None) is None:
                     self._fold_before_shard = bool(opt.fold_zero_grad)
@@ -108,7 +111,15 @@ class VariationalBaseModelVAE:
         return (tuple(data1.shape), tuple(opt.betas), float(opt.eps),
                 float(self.mse_cof), float(self.kl_cof), int(self.batch_size), bool(self.model.training),
                 self.reducer is not None, getattr(self.reducer, "world_size", 1), ops.current_mode(),
-                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic()))
+                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature()
+
+    def _clip_signature(self):
+        """Gradient clipping on/off and the guard change the launches of a step; the VALUE of max_norm does not (a device
+        scalar, FlatAdam.sync_scalars).  Nothing is added while it is off."""
+        opt = self.optimizer
+        if getattr(opt, "max_norm", None) is None:
+            return ()
+        return (("grad_clip", bool(opt.skip_nonfinite)),)
 
     def _eager_train_step(self, data1, data2):
         # (until round 5 the step ran inside an ops.ZeroArena: one clear launch for the outputs that split-k contractions
@@ -260,13 +271,35 @@ class VariationalBaseModelVAE:
         # stalling the queue after every step
         tot = torch.zeros(8, dtype=torch.float64, device=self.device)
         last = None
+        # gradient clipping on: the step's norm (optimizer.clip_state[1]) joins running sum / max tensors the same way; a
+        # norm that is not finite in float32 (a skipped step, or a huge gradient that was clipped) is counted, not averaged
+        opt = self.optimizer
+        clip = getattr(opt, "max_norm", None) is not None
+        self.grad_stats = None
+        if clip:
+            gsum = torch.zeros(2, dtype=torch.float64, device=self.device)      # sum of the finite norms, their number
+            gmax = torch.zeros(1, dtype=torch.float32, device=self.device)
+            zero = torch.zeros(1, dtype=torch.float32, device=self.device)
+            before = opt.clip_state[5:7].clone()
         for data1, data2, speaker_ids in train_loader:
             data1 = data1.to(self.device, non_blocking=True).float()
             data2 = data2.to(self.device, non_blocking=True).float()
             speaker_ids = speaker_ids.view(-1)
             last = self.step_async(data1, data2, speaker_ids)
             tot.add_(last)
-        tot = tot.tolist()
+            if clip:
+                ok = torch.isfinite(opt.clip_state[1:2])
+                norm = torch.where(ok, opt.clip_state[1:2], zero)
+                gsum.add_(torch.cat([norm, ok.float()]))
+                torch.maximum(gmax, norm, out=gmax)
+        if clip:
+            # the epoch's single copy carries them along
+            packed = torch.cat([tot, gsum, gmax.double(), (opt.clip_state[5:7] - before).double()]).tolist()
+            tot = packed[:8]
+            self.grad_stats = {"Grad/Norm mean": packed[8] / max(1.0, packed[9]), "Grad/Norm max": packed[10],
+                               "Grad/Skipped steps": int(packed[11]), "Grad/Clipped steps": int(packed[12])}
+        else:
+            tot = tot.tolist()
         self._check_and_recover()
         last_style = float(last[7]) if last is not None else 0.0
         if hasattr(train_loader, "dataset") and hasattr(train_loader.dataset, "shuffle_data"):
@@ -411,6 +444,8 @@ class VariationalBaseModelVAE:
             rec = {"epoch": epoch, "Loss/Reconstruction Loss1": r1 / nb, "Loss/Reconstruction Loss2": r2 / nb,
                    "Loss/Reconstruction Loss1 hat": r1h / nb, "Loss/Reconstruction Loss2 hat": r2h / nb,
                    "Loss/Z1 KL Loss": k1 / nb, "Loss/Z2 KL Loss": k2 / nb, "Loss/Z KL Style": ks / nb}
+            if getattr(self, "grad_stats", None):       # gradient clipping on (FlatAdam.set_grad_clip): this epoch's norms
+                rec.update(self.grad_stats)
             history.append(rec)
             if self._is_rank0():
                 logging_func(json.dumps(rec))

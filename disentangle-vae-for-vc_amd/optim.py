@@ -11,6 +11,12 @@ host values over when they changed.  The same launch clears the gradient ranges 
 is non-zero: a recurrence that gave up a bounded wait leaves garbage gradients, and weights / moments must not consume
 them before the host has looked (`ops.lstm_pers_check`).
 
+Opt-in (`set_grad_clip`): the global L2 norm of the whole gradient is clipped and a step whose gradient is not finite is
+skipped, ON THE DEVICE inside the same (captured) step: one more pass over the gradient buffer (sum of squares in
+float64, dvae_grad_sumsq), a one-workgroup finalize (norm, coefficient, non-finite flag: `clip_state`) and the Adam launch
+reading its gradient scale from there (dvae_adam_flat_dev_clip).  `max_norm` is a device scalar like the learning rate.
+This is torch.nn.utils.clip_grad_norm_ between backward() and step() of the reference (variational_base_vae.py:68-69).
+
 Replaces torch.optim.Adam(self.model.parameters(), lr) at /root/reference/model/disentangled_vae.py:304
 (betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad).
 """
@@ -68,6 +74,11 @@ class FlatAdam:
         self.dev_state = torch.zeros(8, device=dev, dtype=torch.float32)
         self._dev_scalars = None           # (lr, grad_scale) as last written to dev_state[4:6]
         self._pin, self._pin_ev, self._pin_i = None, None, 0      # pinned staging slots of sync_scalars
+        # gradient clipping / non-finite guard (set_grad_clip): off unless asked for
+        # clip_state: [max_norm, norm, coef, grad_scale * coef, skip this step, skipped steps, clipped steps, not finite]
+        self.max_norm, self.skip_nonfinite = None, True
+        self.clip_state, self._clip_ws = None, None
+        self._dev_max_norm = None          # max_norm as last written to clip_state[0]
         # True: the zero_grad ranges of flat_g are known to be zero (the last Adam launch cleared them after reading and no
         # backward kernel has accumulated since: ops._grad_buf resets it) — zero_grad() is then free
         self._clean = False
@@ -134,24 +145,65 @@ class FlatAdam:
             gs = float(self._dev_scalars[1]) if self._dev_scalars else 1.0
         else:
             gs = float(grad_scale)
-        if self._dev_scalars != (lr, gs):
+        send = self._dev_scalars != (lr, gs)
+        send_clip = self.max_norm is not None and self._dev_max_norm != self.max_norm
+        if send or send_clip:
             if self.dev_state.is_cuda:
                 # staged through a small ring of PINNED slots, asynchronously: a per-step schedule must not stall the host
                 # behind a pageable copy every step; a slot is reused only after the copy that read it has completed
                 if self._pin is None:
-                    self._pin = torch.empty(16, 2, dtype=torch.float32, pin_memory=True)
+                    self._pin = torch.empty(16, 4, dtype=torch.float32, pin_memory=True)
                     self._pin_ev = [None] * 16
                 i = self._pin_i = (self._pin_i + 1) % 16
                 if self._pin_ev[i] is not None:
                     self._pin_ev[i].synchronize()
                 self._pin[i, 0], self._pin[i, 1] = lr, gs
-                self.dev_state[4:6].copy_(self._pin[i], non_blocking=True)
+                if send:
+                    self.dev_state[4:6].copy_(self._pin[i, 0:2], non_blocking=True)
+                if send_clip:
+                    self._pin[i, 2] = self.max_norm
+                    self.clip_state[0:1].copy_(self._pin[i, 2:3], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
                 self._pin_ev[i] = ev
             else:
                 self.dev_state[4:6].copy_(torch.tensor([lr, gs], dtype=torch.float32))
+                if send_clip:
+                    self.clip_state[0] = self.max_norm
             self._dev_scalars = (lr, gs)
+            if send_clip:
+                self._dev_max_norm = self.max_norm
+
+    def set_grad_clip(self, max_norm=None, skip_nonfinite: bool = True):
+        """Clip the global L2 norm of the whole gradient (grad_scale included: under data parallelism the averaged one) to
+        `max_norm` before Adam reads it — torch.nn.utils.clip_grad_norm_, its 1e-6 included — and, with `skip_nonfinite`,
+        skip the step whose gradient holds an inf or a NaN: weights, moments and the step count keep their bits, the
+        gradient ranges are cleared all the same.  None: off, the step launches what it launched without this feature.
+        float("inf"): the norm is measured and the guard is up, nothing is ever clipped.
+        `max_norm` is sent to the device by sync_scalars like the learning rate: changing it between steps costs one small
+        copy and no re-capture; switching the feature on or off changes the launches of a step (the trainer re-captures)."""
+        if max_norm is None:
+            self.max_norm = None
+            return
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError(f"FlatAdam.set_grad_clip: max_norm must be positive (inf: never clip), got {max_norm}")
+        if not self.flat_g.is_cuda:
+            raise RuntimeError("FlatAdam.set_grad_clip: the gradient norm is computed only on the HIP device (no CPU fallback)")
+        if self.clip_state is None:         # allocated once: a captured graph holds their addresses
+            self.clip_state = torch.zeros(8, device=self.flat_g.device, dtype=torch.float32)
+            nbytes = int(lib().dvae_grad_sumsq_ws_bytes(self.numel))
+            self._clip_ws = torch.zeros(nbytes // 8, device=self.flat_g.device, dtype=torch.float64)
+        self.max_norm, self.skip_nonfinite = max_norm, bool(skip_nonfinite)
+
+    def grad_clip_stats(self):
+        """What the last step's finalize left, from ONE device->host copy: norm (of the gradient Adam consumed, before
+        clipping; inf above the float32 range), coef (1.0: not clipped), nonfinite (the gradient held an inf or a NaN),
+        and the running counts of skipped and clipped steps."""
+        if self.clip_state is None:
+            raise RuntimeError("FlatAdam.grad_clip_stats: gradient clipping was never switched on (set_grad_clip)")
+        c = self.clip_state.tolist()
+        return {"norm": c[1], "coef": c[2], "nonfinite": int(c[7]), "skipped": int(c[5]), "clipped": int(c[6])}
 
     def _store_first_guard(self):
         """A store-first parameter is excluded from zero_grad: its gradient must have been WRITTEN exactly once since the
@@ -195,6 +247,9 @@ class FlatAdam:
             if torch.cuda.is_current_stream_capturing():
                 if self._dev_scalars is None or (grad_scale is not None and self._dev_scalars[1] != float(grad_scale)):
                     raise RuntimeError("FlatAdam.step under capture: call sync_scalars(grad_scale) before the capture")
+                if self.max_norm is not None and self._dev_max_norm != self.max_norm:
+                    raise RuntimeError("FlatAdam.step under capture: call sync_scalars(grad_scale) before the capture "
+                                       "(max_norm changed since it was last sent)")
             else:
                 self.sync_scalars(grad_scale)
         skip = None
@@ -209,9 +264,22 @@ class FlatAdam:
             for i, (a, b) in enumerate(spans):
                 rg.lo[i], rg.hi[i] = a, b
         o = 4 * lo
-        check(lib().dvae_adam_flat_dev(self.flat_p.data_ptr() + o, self.flat_g.data_ptr() + o, self.exp_avg.data_ptr() + o,
-                                       self.exp_avg_sq.data_ptr() + o, hi - lo, self.betas[0], self.betas[1], self.eps,
-                                       ptr(self.dev_state), skip, C.byref(rg), int(tick), stream()), "dvae_adam_flat_dev")
+        if self.max_norm is None:
+            check(lib().dvae_adam_flat_dev(self.flat_p.data_ptr() + o, self.flat_g.data_ptr() + o, self.exp_avg.data_ptr() + o,
+                                           self.exp_avg_sq.data_ptr() + o, hi - lo, self.betas[0], self.betas[1], self.eps,
+                                           ptr(self.dev_state), skip, C.byref(rg), int(tick), stream()), "dvae_adam_flat_dev")
+        else:
+            if tick:
+                # the norm of the WHOLE gradient, complete since the fold above: sum of squares, then norm / coefficient /
+                # non-finite flag into clip_state, which the Adam launches of this step (this one and tick=False ones) read
+                check(lib().dvae_grad_sumsq(ptr(self.flat_g), self.numel, ptr(self._clip_ws), stream()), "dvae_grad_sumsq")
+                check(lib().dvae_grad_clip_finalize(ptr(self._clip_ws), self.numel, ptr(self.dev_state), ptr(self.clip_state),
+                                                    skip, int(self.skip_nonfinite), stream()), "dvae_grad_clip_finalize")
+            check(lib().dvae_adam_flat_dev_clip(self.flat_p.data_ptr() + o, self.flat_g.data_ptr() + o,
+                                                self.exp_avg.data_ptr() + o, self.exp_avg_sq.data_ptr() + o, hi - lo,
+                                                self.betas[0], self.betas[1], self.eps, ptr(self.dev_state), skip,
+                                                C.byref(rg), int(tick), ptr(self.clip_state), stream()),
+                  "dvae_adam_flat_dev_clip")
         # the whole buffer was read and cleared only by a full step; a sharded step leaves the other ranks' slices
         # untouched, and says so itself (GradReducer.step)
         self._clean = bool(self.fold_zero_grad) and lo == 0 and hi == self.numel

@@ -67,6 +67,12 @@ def get_parse():
     p.add_argument("--gpu-loader", type=int, default=-1,
                    help="1: device-resident corpus + HIP gather/crop (data.GpuPairLoader); 0: the reference's DataLoader; "
                         "-1: the GPU loader when data parallel, the DataLoader otherwise")
+    p.add_argument("--clip-grad-norm", type=float, default=0.0,
+                   help="clip the global L2 norm of the gradient to this value and skip steps whose gradient is not finite, "
+                        "on the device inside the step (0: off)")
+    p.add_argument("--log-grad-norm", action="store_true", default=False,
+                   help="measure the gradient norm and keep the non-finite guard without clipping (max_norm = inf); "
+                        "scalars.jsonl gains the Grad/... keys either way")
     return p
 
 
@@ -247,6 +253,10 @@ def main(argv=None):
                               args.log_interval, args.normalize, speaker_size=args.speaker_size, device=device,
                               latent_dim=args.latent_size, beta=args.beta_cof, batch_size=args.batch_size,
                               mse_cof=args.mse_cof, kl_cof=args.kl_cof, style_cof=args.style_cof)
+    if args.clip_grad_norm < 0:
+        raise SystemExit(f"--clip-grad-norm {args.clip_grad_norm}: a positive norm, or 0 for off")
+    if args.clip_grad_norm > 0 or args.log_grad_norm:
+        vsc.optimizer.set_grad_clip(args.clip_grad_norm if args.clip_grad_norm > 0 else float("inf"))
     dp = world > 1 or os.environ.get("DVAE_FORCE_DDP", "0") == "1"
     if dp:
         setup_data_parallel(vsc, args.seed)

@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 312
+#define DVAE_ABI_VERSION 313
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -393,6 +393,32 @@ typedef struct {
 } dvae_ranges_t;
 int dvae_adam_flat_dev(float* p, float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
                        float* state, const unsigned* skip_if_nonzero, const dvae_ranges_t* clear, int tick, void* stream);
+
+/* ---- global gradient-norm clipping and a non-finite step guard, on the device inside the (captured) step ----
+ * Replaces torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) between loss.backward() and optimizer.step()
+ * (variational_base_vae.py:68 and :69; the reference leaves room for it, its gradients being ordinary tensors there).
+ * Three launches in place of dvae_adam_flat_dev's two-launch step:
+ * dvae_grad_sumsq: one pass over g[0, n) (n % 4 == 0, 16-byte aligned), sum of g^2 accumulated in float64; every workgroup
+ *   stores one float64 partial into ws (>= dvae_grad_sumsq_ws_bytes(n) bytes, 8-byte aligned).  No atomics: grid and
+ *   summation order depend on n alone, the result is bit-identical from run to run.
+ * dvae_grad_clip_finalize: adds the partials in a fixed order and, in float64, rounding once per store, fills clip (float[8],
+ *   zero-initialised by the caller, [0] written by it — optim.FlatAdam.sync_scalars — outside any capture):
+ *     [0] max_norm (+inf: measure and guard, never clip)
+ *     [1] norm = state[5] * sqrt(sum): of the gradient Adam consumes (grad_scale included); +inf above FLT_MAX
+ *     [2] coef = min(1, max_norm / (norm + 1e-6))          [3] eff = state[5] * coef: == state[5] bit for bit when coef == 1
+ *     [4] 1 while this step is skipped: the sum is not finite (<=> some element is not: the square of a finite float32
+ *         cannot overflow a double) and guard_nonfinite != 0; else 0
+ *     [5] skipped steps so far     [6] clipped steps so far (coef < 1)     [7] 1 when the sum is not finite, guarded or not
+ *   `state` is dvae_adam_flat_dev's; n is the n given to dvae_grad_sumsq.  While *skip_if_nonzero != 0 it changes nothing.
+ * dvae_adam_flat_dev_clip: dvae_adam_flat_dev reading clip[3] in place of state[5]; while clip[4] != 0 t does not advance
+ *   and p, m, v are not written, but the `clear` ranges of g are still zeroed (the next backward accumulates into them). */
+int64_t dvae_grad_sumsq_ws_bytes(int64_t n);
+int dvae_grad_sumsq(const float* g, int64_t n, void* ws, void* stream);
+int dvae_grad_clip_finalize(const void* ws, int64_t n, const float* state, float* clip,
+                            const unsigned* skip_if_nonzero, int guard_nonfinite, void* stream);
+int dvae_adam_flat_dev_clip(float* p, float* g, float* m, float* v, int64_t n, float beta1, float beta2, float eps,
+                            float* state, const unsigned* skip_if_nonzero, const dvae_ranges_t* clear, int tick,
+                            const float* clip, void* stream);
 
 /* x[0, n) = 0 (16-byte aligned): optimizer.zero_grad() (variational_base_vae.py:86) and the outputs that split-k
  * contractions accumulate into atomically, zeroed by a launch of their own right in front of the accumulation. */
