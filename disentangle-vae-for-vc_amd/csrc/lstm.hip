@@ -1174,7 +1174,8 @@ int dvae_pers_fwd_units(int N, int H);
 int dvae_pers_launch(const dvae_lstm_dir_t& d, bool bwd, int T, int N, int H, int64_t ldh, int drop_bid, hipStream_t s);
 
 namespace {
-// Kernel families, chosen by H (and, for the persistent one, by the caller handing in a workspace) (every one of them is reached by tests/test_hip_kernels.py::test_lstm_layer):
+// Kernel families, chosen by H (and, for the persistent one, by the caller handing in a workspace) (every one of them, in every arithmetic and tile
+// height, is held frame by frame to a float64 LSTM by tests/test_hip_lstm.py; tests/lstm_ref.py CASES lists the shape that reaches each):
 //   H == 64            lstm_seq_*_h64      whole sequence in one launch, W_hh in registers
 //   H % 512 == 0       lstm_step_*_v5      one launch per frame, fragment-packed W_hh (needs dirs[i].w_packed)
 //   other H % 64 == 0  lstm_step_*_kernel  one launch per frame, W_hh staged through LDS (generic fallback)
