@@ -61,7 +61,7 @@ COMPUTE_MODES = {"fp32": MODE_F32, "f32": MODE_F32, "float32": MODE_F32, "bf16":
                  "fp32x3": MODE_F32X3, "f32x3": MODE_F32X3}
 
 DEFAULT_COMPUTE_DTYPE = "fp32x3"
-ABI_VERSION = 313     # DVAE_ABI_VERSION of include/dvae_hip.h
+ABI_VERSION = 314     # DVAE_ABI_VERSION of include/dvae_hip.h
 
 # name -> (restype, argtypes); mirrors include/dvae_hip.h one to one
 SIGNATURES = {
@@ -120,6 +120,9 @@ SIGNATURES = {
     "dvae_grad_sumsq_ws_bytes": (i64, [i64]),
     "dvae_grad_sumsq": (i32, [vp, i64, vp, vp]),
     "dvae_grad_clip_finalize": (i32, [vp, i64, vp, vp, vp, i32, vp]),
+    "dvae_ema_tick": (i32, [vp, vp, vp, vp]),
+    "dvae_ema_update": (i32, [vp, vp, i64, vp, vp]),
+    "dvae_swap_f32": (i32, [vp, vp, i64, vp]),
     "dvae_lstm_pers_err_word": (vp, [vp]),
     "dvae_sum_f32": (i32, [vp, vp, vp, vp, i64, vp]),
     "dvae_zero_f32": (i32, [vp, i64, vp]),

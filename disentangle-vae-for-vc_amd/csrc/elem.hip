@@ -452,6 +452,78 @@ __global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double* _
   else if (coef < 1.0) clip[6] += 1.f;
 }
 
+// ------------------------------------------------------------------ exponential moving average of the weights
+// e <- e + w (p - e) after the Adam launch(es) of a full step, inside the same (captured) step: a tick that decides whether
+// this step counts and what it weighs, then one sweep over the two flat buffers.  es: float[8]
+//   [0] decay (host-written)   [1] k: updates applied so far   [2] w = 1 - d_k of the last update
+//   [3] warm-up on/off (host-written)   [4] 1 while this step's update is applied, 0 while it is skipped   [5..7] never written
+// A step is skipped on the conditions adam_tick_kernel<CLIP> skips on: the error word of the persistent LSTM launches, or
+// clip[4] (the gradient was not finite) — the weights did not move, so the average must not move towards them either.
+__global__ void ema_tick_kernel(float* __restrict__ es, const unsigned* __restrict__ skip, const float* __restrict__ clip) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    if ((skip && __hip_atomic_load(skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) || (clip && clip[4] != 0.f)) {
+      es[4] = 0.f;
+      return;
+    }
+    const double k = (double)es[1] + 1.0;
+    double d = (double)es[0];
+    if (es[3] != 0.f) {
+      const double ramp = (1.0 + k) / (10.0 + k);       // the first updates follow the weights, not the initial values
+      d = ramp < d ? ramp : d;
+    }
+    es[1] = (float)k;
+    es[2] = (float)(1.0 - d);                           // rounded once
+    es[4] = 1.f;
+  }
+}
+
+// Shaped like adam_dev_kernel: U independent 16-byte accesses per tensor and thread per trip, clamped tail, streamed once.
+// 8 bytes read, 4 written per parameter; every element depends on its own index alone.
+template <int U>
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, int64_t n4,
+                                                         const float* __restrict__ es) {
+  if (es[4] == 0.f) return;
+  const float w = es[2];
+  for (int64_t i0 = (int64_t)blockIdx.x * (256 * U) + threadIdx.x; i0 < n4; i0 += (int64_t)gridDim.x * (256 * U)) {
+    f32x4 ee[U], pp[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * 256 < n4 ? i0 + u * 256 : i0;
+      ee[u] = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(e + 4 * i));
+      pp[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + 4 * i));
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * 256;
+      if (i >= n4) break;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ee[u][k] = fmaf(w, pp[u][k] - ee[u][k], ee[u][k]);
+      __builtin_nontemporal_store(ee[u], reinterpret_cast<f32x4*>(e + 4 * i));
+    }
+  }
+}
+
+// a <-> b, exactly (bits are moved, never computed with)
+template <int U>
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n4) {
+  for (int64_t i0 = (int64_t)blockIdx.x * (256 * U) + threadIdx.x; i0 < n4; i0 += (int64_t)gridDim.x * (256 * U)) {
+    f32x4 aa[U], bb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * 256 < n4 ? i0 + u * 256 : i0;
+      aa[u] = *reinterpret_cast<const f32x4*>(a + 4 * i);
+      bb[u] = *reinterpret_cast<const f32x4*>(b + 4 * i);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * 256;
+      if (i >= n4) break;
+      *reinterpret_cast<f32x4*>(a + 4 * i) = bb[u];
+      *reinterpret_cast<f32x4*>(b + 4 * i) = aa[u];
+    }
+  }
+}
+
 // ------------------------------------------------------------------ layout
 // X[t][g*Bh+b][c] = x_g[b][c][t] ; tile-transpose through LDS over (c,t) per segment
 template <bool OB16>
@@ -880,6 +952,36 @@ DVAE_API int dvae_grad_clip_finalize(const void* ws, int64_t n, const float* sta
   hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const double*>(ws), sumsq_blocks(n), state, clip, skip_if_nonzero,
                      guard_nonfinite ? 1 : 0);
+  return dvae_check_launch();
+}
+
+constexpr int EMA_U = 2;          // 16-byte loads in flight per tensor, thread and trip (ema_update_kernel, swap_kernel)
+static bool flat_pair_ok(const float* a, const float* b, int64_t n) {
+  if (!a || !b || n < 4 || (n & 3) || ((((uintptr_t)a) | ((uintptr_t)b)) & 15)) return false;
+  const uintptr_t lo = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)a : (uintptr_t)b;
+  const uintptr_t hi = (uintptr_t)a < (uintptr_t)b ? (uintptr_t)b : (uintptr_t)a;
+  return hi - lo >= (uintptr_t)n * sizeof(float);      // the two buffers do not overlap
+}
+
+DVAE_API int dvae_ema_tick(float* ema_state, const unsigned* skip_if_nonzero, const float* clip_or_null, void* stream) {
+  if (!ema_state) return DVAE_EINVAL;
+  hipLaunchKernelGGL(ema_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ema_state, skip_if_nonzero, clip_or_null);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_ema_update(float* ema, const float* p, int64_t n, const float* ema_state, void* stream) {
+  if (!ema_state || !flat_pair_ok(ema, p, n)) return DVAE_EINVAL;
+  const int64_t n4 = n >> 2;
+  hipLaunchKernelGGL(ema_update_kernel<EMA_U>, dim3(nblk((n4 + EMA_U - 1) / EMA_U, 256, 2048)), dim3(256), 0,
+                     (hipStream_t)stream, ema, p, n4, ema_state);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_swap_f32(float* a, float* b, int64_t n, void* stream) {
+  if (!flat_pair_ok(a, b, n)) return DVAE_EINVAL;
+  const int64_t n4 = n >> 2;
+  hipLaunchKernelGGL(swap_kernel<EMA_U>, dim3(nblk((n4 + EMA_U - 1) / EMA_U, 256, 2048)), dim3(256), 0,
+                     (hipStream_t)stream, a, b, n4);
   return dvae_check_launch();
 }
 

@@ -34,6 +34,14 @@ def refuse_sharded_clip(optimizer):
                          "set_grad_clip(None)")
 
 
+def refuse_sharded_ema(optimizer):
+    """The weight average follows a FULL step: after a sharded one (mode "rs_ag") a rank holds the other ranks' new weights
+    only once the all-gather has landed, and no run with several ranks exists to hold an average built there to anything."""
+    if getattr(optimizer, "ema_decay", None) is not None:
+        raise ValueError("a weight average (FlatAdam.set_ema) with a sharded optimizer step (GradReducer mode 'rs_ag') is not "
+                         "supported: it needs the gathered weights; use mode 'all_reduce' or set_ema(None)")
+
+
 class GradReducer:
     """mode "all_reduce" (default): every bucket is summed over the ranks in place (dist.all_reduce) and every rank
     runs the full Adam launch over all parameters.
@@ -189,6 +197,7 @@ class GradReducer:
             optimizer.step(grad_scale=scale)      # every rank holds the whole reduced gradient: one norm, the same everywhere
             return
         refuse_sharded_clip(optimizer)
+        refuse_sharded_ema(optimizer)
         flat_p = optimizer.flat_p
         works = []
         for b, (lo, hi) in enumerate(self.buckets):

@@ -65,8 +65,9 @@ class VariationalBaseModelVAE:
     def attach_reducer(self, reducer):
         sharded = reducer is not None and getattr(reducer, "mode", "all_reduce") == "rs_ag"
         if sharded and self.optimizer is not None:
-            from ..ddp import refuse_sharded_clip
+            from ..ddp import refuse_sharded_clip, refuse_sharded_ema
             refuse_sharded_clip(self.optimizer)     # ValueError, and nothing attached: a shard's norm is not the gradient's
+            refuse_sharded_ema(self.optimizer)      # likewise: the average needs the gathered weights
         self.reducer = reducer
         if self.optimizer is not None:
             # a sharded step (rs_ag) reads — and could clear — only this rank's slices of the gradient buffer: zero_grad
@@ -111,7 +112,7 @@ class VariationalBaseModelVAE:
         return (tuple(data1.shape), tuple(opt.betas), float(opt.eps),
                 float(self.mse_cof), float(self.kl_cof), int(self.batch_size), bool(self.model.training),
                 self.reducer is not None, getattr(self.reducer, "world_size", 1), ops.current_mode(),
-                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature()
+                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature()
 
     def _clip_signature(self):
         """Gradient clipping on/off and the guard change the launches of a step; the VALUE of max_norm does not (a device
@@ -120,6 +121,17 @@ class VariationalBaseModelVAE:
         if getattr(opt, "max_norm", None) is None:
             return ()
         return (("grad_clip", bool(opt.skip_nonfinite)),)
+
+    def _ema_signature(self):
+        """The weight average on/off changes the launches of a step; its decay and warm-up do not (device scalars).  Nothing
+        is added while it is off."""
+        return (("ema",),) if getattr(self.optimizer, "ema_decay", None) is not None else ()
+
+    def ema_weights(self):
+        """`with trainer.ema_weights(): ...` — forward passes, conversion and probing inside the body run on the averaged
+        weights (FlatAdam.set_ema); the weights come back when it leaves.  BatchNorm running statistics are buffers, moving
+        averages already, and are the same inside and outside."""
+        return self.optimizer.ema_weights()
 
     def _eager_train_step(self, data1, data2):
         # (until round 5 the step ran inside an ops.ZeroArena: one clear launch for the outputs that split-k contractions
@@ -276,6 +288,8 @@ class VariationalBaseModelVAE:
         opt = self.optimizer
         clip = getattr(opt, "max_norm", None) is not None
         self.grad_stats = None
+        ema = getattr(opt, "ema_decay", None) is not None
+        self.ema_stats = None
         if clip:
             gsum = torch.zeros(2, dtype=torch.float64, device=self.device)      # sum of the finite norms, their number
             gmax = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -294,12 +308,18 @@ class VariationalBaseModelVAE:
                 torch.maximum(gmax, norm, out=gmax)
         if clip:
             # the epoch's single copy carries them along
-            packed = torch.cat([tot, gsum, gmax.double(), (opt.clip_state[5:7] - before).double()]).tolist()
+            packed = torch.cat([tot, gsum, gmax.double(), (opt.clip_state[5:7] - before).double()]
+                               + ([opt.ema_state[1:3].double()] if ema else [])).tolist()
             tot = packed[:8]
             self.grad_stats = {"Grad/Norm mean": packed[8] / max(1.0, packed[9]), "Grad/Norm max": packed[10],
                                "Grad/Skipped steps": int(packed[11]), "Grad/Clipped steps": int(packed[12])}
+        elif ema:
+            packed = torch.cat([tot, opt.ema_state[1:3].double()]).tolist()
+            tot = packed[:8]
         else:
             tot = tot.tolist()
+        if ema:
+            self.ema_stats = {"EMA/Updates": int(packed[-2]), "EMA/Weight": packed[-1]}
         self._check_and_recover()
         last_style = float(last[7]) if last is not None else 0.0
         if hasattr(train_loader, "dataset") and hasattr(train_loader.dataset, "shuffle_data"):
@@ -310,7 +330,9 @@ class VariationalBaseModelVAE:
         return tot[1], tot[2], tot[3], tot[4], tot[5], tot[6], last_style
 
     # ---- variational_base_vae.py:127-149
-    def load_last_model(self, checkpoints_path, logging_func=print):
+    def load_last_model(self, checkpoints_path, logging_func=print, use_ema=False):
+        """use_ema: take the weights from `<base>.ema.pth` (the averaged weights run_training writes next to `<base>.pth`
+        while FlatAdam.set_ema is on) in place of `<base>.pth`.  A `<epoch>.ema` stem is never a checkpoint candidate."""
         name = self.model.__class__.__name__
         ids = []
         for f in glob(f"{checkpoints_path}/*.pth"):
@@ -321,7 +343,13 @@ class VariationalBaseModelVAE:
             logging_func(f"Training {name} model from scratch...")
             return 1
         start_epoch, last = max(ids, key=lambda it: it[0])
-        self.model.load_state_dict(torch.load(last, map_location=self.device))
+        weights = last
+        if use_ema:
+            weights = last[:-4] + ".ema.pth"
+            if not os.path.exists(weights):
+                raise FileNotFoundError(f"{weights} is missing: the last checkpoint ({last}) was written without a weight "
+                                        "average (train with --ema-decay / FlatAdam.set_ema)")
+        self.model.load_state_dict(torch.load(weights, map_location=self.device))
         opt = last[:-4] + ".opt"
         if os.path.exists(opt):
             sd = torch.load(opt, map_location="cpu")
@@ -446,6 +474,8 @@ class VariationalBaseModelVAE:
                    "Loss/Z1 KL Loss": k1 / nb, "Loss/Z2 KL Loss": k2 / nb, "Loss/Z KL Style": ks / nb}
             if getattr(self, "grad_stats", None):       # gradient clipping on (FlatAdam.set_grad_clip): this epoch's norms
                 rec.update(self.grad_stats)
+            if getattr(self, "ema_stats", None):        # weight average on (FlatAdam.set_ema)
+                rec.update(self.ema_stats)
             history.append(rec)
             if self._is_rank0():
                 logging_func(json.dumps(rec))
@@ -465,6 +495,11 @@ class VariationalBaseModelVAE:
                     gen = torch.cuda.default_generators[torch.device(self.device).index or 0]
                     osd["cuda_rng_seed"], osd["cuda_rng_offset"] = int(gen.initial_seed()), int(gen.get_offset())
                     torch.save(osd, base + ".opt")
+                    if getattr(self.optimizer, "ema_decay", None) is not None:
+                        # the very state_dict above with every parameter replaced by its average; buffers (BatchNorm
+                        # running statistics) are the same tensors in both files
+                        with self.ema_weights():
+                            torch.save(self.model.state_dict(), base + ".ema.pth")
                 # variational_base_vae.py:196-201: reconstructions of one test batch from the checkpoint just written
                 if estimation_dir and test_loader is not None:
                     self.estimate_trained_model(test_loader, checkpoints_path, estimation_dir)

@@ -17,6 +17,14 @@ float64, dvae_grad_sumsq), a one-workgroup finalize (norm, coefficient, non-fini
 reading its gradient scale from there (dvae_adam_flat_dev_clip).  `max_norm` is a device scalar like the learning rate.
 This is torch.nn.utils.clip_grad_norm_ between backward() and step() of the reference (variational_base_vae.py:68-69).
 
+Opt-in (`set_ema`): an exponential moving average of the weights, `self.ema`, a second flat buffer shaped like `flat_p`,
+updated ON THE DEVICE after the Adam launch of a full step and inside the same (captured) step: a one-workgroup tick
+(dvae_ema_tick: does this step count — the conditions Adam skips on — and with what weight: `ema_state`) and one sweep
+(dvae_ema_update: 8 bytes read, 4 written per parameter).  `decay` is a device scalar like the learning rate.  `swap_ema()`
+/ `ema_weights()` exchange weights and average IN PLACE (dvae_swap_f32): every parameter stays the view it was, the
+captured graph stays valid, and every forward entry point re-derives its operand layouts from `flat_p` anyway.
+New functionality: the reference keeps the last iterate only.
+
 Replaces torch.optim.Adam(self.model.parameters(), lr) at /root/reference/model/disentangled_vae.py:304
 (betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad).
 """
@@ -79,6 +87,12 @@ class FlatAdam:
         self.max_norm, self.skip_nonfinite = None, True
         self.clip_state, self._clip_ws = None, None
         self._dev_max_norm = None          # max_norm as last written to clip_state[0]
+        # moving average of the weights (set_ema): off unless asked for
+        # ema_state: [decay, updates applied, weight of the last update, warm-up, this step's update applied, -, -, -]
+        self.ema_decay, self.ema_warmup = None, True
+        self.ema, self.ema_state = None, None
+        self._dev_ema = None               # (decay, warmup) as last written to ema_state[0], [3]
+        self.ema_swapped = False           # True: flat_p holds the average and self.ema the weights (swap_ema)
         # True: the zero_grad ranges of flat_g are known to be zero (the last Adam launch cleared them after reading and no
         # backward kernel has accumulated since: ops._grad_buf resets it) — zero_grad() is then free
         self._clean = False
@@ -147,12 +161,13 @@ class FlatAdam:
             gs = float(grad_scale)
         send = self._dev_scalars != (lr, gs)
         send_clip = self.max_norm is not None and self._dev_max_norm != self.max_norm
-        if send or send_clip:
+        send_ema = self.ema_decay is not None and self._dev_ema != (self.ema_decay, self.ema_warmup)
+        if send or send_clip or send_ema:
             if self.dev_state.is_cuda:
                 # staged through a small ring of PINNED slots, asynchronously: a per-step schedule must not stall the host
                 # behind a pageable copy every step; a slot is reused only after the copy that read it has completed
                 if self._pin is None:
-                    self._pin = torch.empty(16, 4, dtype=torch.float32, pin_memory=True)
+                    self._pin = torch.empty(16, 8, dtype=torch.float32, pin_memory=True)
                     self._pin_ev = [None] * 16
                 i = self._pin_i = (self._pin_i + 1) % 16
                 if self._pin_ev[i] is not None:
@@ -163,6 +178,10 @@ class FlatAdam:
                 if send_clip:
                     self._pin[i, 2] = self.max_norm
                     self.clip_state[0:1].copy_(self._pin[i, 2:3], non_blocking=True)
+                if send_ema:        # [0] and [3] lie on either side of what the tick launch writes: 4 bytes each
+                    self._pin[i, 4], self._pin[i, 5] = self.ema_decay, float(self.ema_warmup)
+                    self.ema_state[0:1].copy_(self._pin[i, 4:5], non_blocking=True)
+                    self.ema_state[3:4].copy_(self._pin[i, 5:6], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record()
                 self._pin_ev[i] = ev
@@ -173,6 +192,8 @@ class FlatAdam:
             self._dev_scalars = (lr, gs)
             if send_clip:
                 self._dev_max_norm = self.max_norm
+            if send_ema:
+                self._dev_ema = (self.ema_decay, self.ema_warmup)
 
     def set_grad_clip(self, max_norm=None, skip_nonfinite: bool = True):
         """Clip the global L2 norm of the whole gradient (grad_scale included: under data parallelism the averaged one) to
@@ -205,6 +226,76 @@ class FlatAdam:
         c = self.clip_state.tolist()
         return {"norm": c[1], "coef": c[2], "nonfinite": int(c[7]), "skipped": int(c[5]), "clipped": int(c[6])}
 
+    def set_ema(self, decay=None, warmup: bool = True, reset: bool = False):
+        """Keep an exponential moving average of the weights in `self.ema`: after every full step that Adam applied,
+        ema += w (p - ema) with w = 1 - d, d = decay, or with `warmup` d = min(decay, (1 + k) / (10 + k)) at the k-th update
+        (the first updates then follow the weights instead of holding on to the initial values).  A step Adam skips (the
+        non-finite guard of set_grad_clip, the error word of the persistent LSTM launches) leaves the average alone.
+        The first call allocates the buffer — once: a captured graph holds its address — and starts it from the weights;
+        later calls change `decay` / `warmup` only, which sync_scalars sends to the device like the learning rate: a small
+        copy and no re-capture, while switching the average on or off changes the launches of a step (the trainer
+        re-captures).  reset: start over from the current weights with no update counted.  None: the updates stop, the
+        average stays where it is and stays usable for swap_ema / ema_weights / state_dict.
+        Only parameters are averaged: BatchNorm running statistics are buffers, moving averages already, and not touched."""
+        if decay is None:
+            self.ema_decay = None
+            return
+        decay = float(decay)
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"FlatAdam.set_ema: decay must be in [0, 1), got {decay}")
+        if not self.flat_p.is_cuda:
+            raise RuntimeError("FlatAdam.set_ema: the average is kept only on the HIP device (no CPU fallback)")
+        if self.ema is None:                # allocated once: a captured graph holds their addresses
+            self.ema = torch.empty_like(self.flat_p)
+            self.ema_state = torch.zeros(8, device=self.flat_p.device, dtype=torch.float32)
+            reset = True
+        if reset:
+            if self.ema_swapped:
+                raise RuntimeError("FlatAdam.set_ema(reset=True) while the average is swapped in (swap_ema): flat_p holds "
+                                   "the average, not the weights")
+            self.ema.copy_(self.flat_p)
+            self.ema_state[1:3].zero_()
+            self.ema_state[4:5].zero_()
+        self.ema_decay, self.ema_warmup = decay, bool(warmup)
+
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise RuntimeError(f"FlatAdam.{what}: the weight average was never switched on (set_ema)")
+
+    def ema_stats(self):
+        """What the last step's tick left, from ONE device->host copy: the updates applied so far, the weight 1 - d of the
+        last one, the decay the device holds, and whether the last step's update was applied (1) or skipped (0)."""
+        self._need_ema("ema_stats")
+        c = self.ema_state.tolist()
+        return {"updates": int(c[1]), "weight": c[2], "decay": c[0], "applied": int(c[4])}
+
+    def swap_ema(self):
+        """Exchange the weights and their average in place: afterwards every parameter (a view of flat_p) reads the
+        average, and `self.ema` holds the weights until the next call swaps them back.  step() refuses while swapped."""
+        self._need_ema("swap_ema")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FlatAdam.swap_ema: not inside a graph capture")
+        check(lib().dvae_swap_f32(ptr(self.flat_p), ptr(self.ema), self.numel, stream()), "dvae_swap_f32")
+        self.ema_swapped = not self.ema_swapped
+
+    def ema_weights(self):
+        """`with opt.ema_weights(): ...` — the body sees the averaged weights; the weights come back when it leaves, also
+        through an exception."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def swapped():
+            self.swap_ema()
+            try:
+                yield self
+            finally:
+                self.swap_ema()
+        return swapped()
+
+    def _ema_views(self):
+        """the average per parameter, whichever side of a swap it is on"""
+        return self._moment_views(self.flat_p if self.ema_swapped else self.ema)
+
     def _store_first_guard(self):
         """A store-first parameter is excluded from zero_grad: its gradient must have been WRITTEN exactly once since the
         last step (ops.LinearFn.backward counts), else Adam would consume a stale or a partial gradient."""
@@ -235,6 +326,9 @@ class FlatAdam:
         import ctypes as C
         if lo % 4 or hi % 4 or not 0 <= lo < hi <= self.numel:
             raise ValueError(f"FlatAdam.step_range: [{lo}, {hi}) is not a 16-byte aligned range of the flat buffers")
+        if self.ema_swapped:
+            raise RuntimeError("FlatAdam.step while the weight average is swapped in (swap_ema / ema_weights): Adam would "
+                               "move the average and average the weights; swap back first")
         if tick:
             if not self.views_intact():
                 # model.zero_grad() (set_to_none), .to()/.float() or `p.grad = None` would detach parameters from the flat
@@ -250,6 +344,9 @@ class FlatAdam:
                 if self.max_norm is not None and self._dev_max_norm != self.max_norm:
                     raise RuntimeError("FlatAdam.step under capture: call sync_scalars(grad_scale) before the capture "
                                        "(max_norm changed since it was last sent)")
+                if self.ema_decay is not None and self._dev_ema != (self.ema_decay, self.ema_warmup):
+                    raise RuntimeError("FlatAdam.step under capture: call sync_scalars(grad_scale) before the capture "
+                                       "(the EMA decay changed since it was last sent)")
             else:
                 self.sync_scalars(grad_scale)
         skip = None
@@ -280,6 +377,12 @@ class FlatAdam:
                                                 self.betas[0], self.betas[1], self.eps, ptr(self.dev_state), skip,
                                                 C.byref(rg), int(tick), ptr(self.clip_state), stream()),
                   "dvae_adam_flat_dev_clip")
+        if self.ema_decay is not None and tick and lo == 0 and hi == self.numel:
+            # a full step only: a partial range (a sharded optimizer's) never moves the average
+            check(lib().dvae_ema_tick(ptr(self.ema_state), skip, ptr(self.clip_state) if self.max_norm is not None else None,
+                                      stream()), "dvae_ema_tick")
+            check(lib().dvae_ema_update(ptr(self.ema), ptr(self.flat_p), self.numel, ptr(self.ema_state), stream()),
+                  "dvae_ema_update")
         # the whole buffer was read and cleared only by a full step; a sharded step leaves the other ranks' slices
         # untouched, and says so itself (GradReducer.step)
         self._clean = bool(self.fold_zero_grad) and lo == 0 and hi == self.numel
@@ -305,11 +408,17 @@ class FlatAdam:
     def state_dict(self):
         """Moments per parameter in the reference's layout (what torch.optim.Adam would hold for the reference model):
         independent of the packed conv-weight storage and of the order of the flat buffer."""
-        return {"format": self.STATE_FORMAT, "t": self.t, "lr": self.param_groups[0]["lr"], "betas": self.betas,
-                "eps": self.eps, "names": list(self.names),
-                "exp_avg": {n: self._to_ref(n, v).detach().cpu().contiguous() for n, v in self._moment_views(self.exp_avg)},
-                "exp_avg_sq": {n: self._to_ref(n, v).detach().cpu().contiguous()
-                               for n, v in self._moment_views(self.exp_avg_sq)}}
+        sd = {"format": self.STATE_FORMAT, "t": self.t, "lr": self.param_groups[0]["lr"], "betas": self.betas,
+              "eps": self.eps, "names": list(self.names),
+              "exp_avg": {n: self._to_ref(n, v).detach().cpu().contiguous() for n, v in self._moment_views(self.exp_avg)},
+              "exp_avg_sq": {n: self._to_ref(n, v).detach().cpu().contiguous()
+                             for n, v in self._moment_views(self.exp_avg_sq)}}
+        if self.ema is not None:            # configured (set_ema), running or stopped: the average, like the moments
+            st = self.ema_stats()
+            sd["ema"] = {"decay": self.ema_decay if self.ema_decay is not None else st["decay"], "warmup": self.ema_warmup,
+                         "updates": st["updates"],
+                         "avg": {n: self._to_ref(n, v).detach().cpu().contiguous() for n, v in self._ema_views()}}
+        return sd
 
     def load_state_dict(self, sd, legacy_layout=None):
         """legacy_layout: only for format-1 files (see below): "packed" | "torch"."""
@@ -356,3 +465,23 @@ class FlatAdam:
                 if tuple(src.shape) != want:
                     raise ValueError(f"optimizer state of {n}: shape {tuple(src.shape)}, expected {want}")
                 v.copy_(self._from_ref(n, src.to(v.device)))
+        if self.ema is not None:
+            # the average continues from the file when it has one (the decay stays the caller's); else it starts from the
+            # weights as they are now — load the model's weights first — with no update counted
+            if self.ema_swapped:
+                raise RuntimeError("FlatAdam.load_state_dict while the weight average is swapped in (swap_ema)")
+            saved = sd.get("ema")
+            if saved is None:
+                self.ema.copy_(self.flat_p)
+                updates = 0.0
+            else:
+                for n, v in self._moment_views(self.ema):
+                    src = saved["avg"][n]
+                    want = tuple(self._to_ref(n, v).shape)
+                    if tuple(src.shape) != want:
+                        raise ValueError(f"optimizer state, average of {n}: shape {tuple(src.shape)}, expected {want}")
+                    v.copy_(self._from_ref(n, src.to(v.device)))
+                updates = float(saved["updates"])
+            self.ema_state[1:3].zero_()
+            self.ema_state[4:5].zero_()
+            self.ema_state[1] = updates

@@ -2,7 +2,7 @@
 carry the speaker while the CONTENT latent does not?
 
     python -m dvae_amd.probe <corpus> --log_dir <run> [--max_utts N] [--epochs E] [--seed S] [--json PATH]
-                                      [--score DIR --speaker NAME]
+                                      [--score DIR --speaker NAME] [--use-ema]
 
 The reference's hook is a speaker classifier on latents, model/feature_selection.py:5-43 trained by
 model/train_feature_selection.py:10-61 — written for an older model (`sparse_encoding`, 512-wide latents), with a softmax
@@ -396,6 +396,8 @@ def _parse(argv):
     p.add_argument("--json", type=Path, default=None, help="where to write the results (default <log_dir>/probe.json)")
     p.add_argument("--score", type=Path, default=None, help="directory of converted 16 kHz .wav files to classify")
     p.add_argument("--speaker", type=str, default=None, help="--score: the target speaker (a directory name of the corpus)")
+    p.add_argument("--use-ema", action="store_true", default=False,
+                   help="encode with the averaged weights (<name>_<epoch>.ema.pth of a --ema-decay run)")
     return p.parse_args(argv)
 
 
@@ -443,13 +445,17 @@ def main(argv=None) -> int:
                               latent_dim=latent, beta=float(cfg.get("beta_cof", 0.1)),
                               batch_size=int(cfg.get("batch_size", 2)), mse_cof=float(cfg.get("mse_cof", 10)),
                               kl_cof=float(cfg.get("kl_cof", 10)), style_cof=float(cfg.get("style_cof", 0.1)))
-    next_epoch = vsc.load_last_model(str(ckpt_dir), logging_func=lambda *_: None)
+    try:
+        next_epoch = vsc.load_last_model(str(ckpt_dir), logging_func=lambda *_: None, use_ema=args.use_ema)
+    except FileNotFoundError as e:
+        err(f"--use-ema: {e}")
+        return 1
     style_mu, content_mu = encode_corpus(vsc, chunks)
     torch.cuda.synchronize()
     vsc._check_device_errors()
     n_ho_utt = sum(1 for u in chunks.utterances if u["held_out"])
     result = dict(corpus=str(args.corpus), log_dir=str(args.log_dir), checkpoint_epoch=int(next_epoch) - 1, n_frames=T,
-                  seed=args.seed, epochs=args.epochs, max_utts=args.max_utts, speakers=chunks.speakers,
+                  use_ema=bool(args.use_ema), seed=args.seed, epochs=args.epochs, max_utts=args.max_utts, speakers=chunks.speakers,
                   chance=1.0 / len(chunks.speakers), n_train_chunks=int((~chunks.held_out).sum()),
                   n_held_out_chunks=int(chunks.held_out.sum()), n_train_utterances=len(chunks.utterances) - n_ho_utt,
                   n_held_out_utterances=n_ho_utt, skipped=list(chunks.skipped), probes={})

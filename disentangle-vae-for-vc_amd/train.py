@@ -7,6 +7,8 @@ Kept flags: --batch-size --latent-size --speaker_size --lr --epochs --report-int
 --dataset_fp --log_dir --train --samples_length (honoured here; the reference parses it but hard-codes 64,
 train.py:53).  Parsed-and-ignored flags of the reference (--hidden-size --alpha --normalize --beta_cof --style_cof
 --sample-size --no-cuda --do-not-resume --log-interval) are accepted for command-line compatibility.
+--ema-decay F (new): an exponential moving average of the weights, kept on the device inside the step (optim.FlatAdam.set_ema)
+and written as <name>_<epoch>.ema.pth next to every checkpoint; --use-ema makes --convert voice it.
 --convert (reference variational_base_vae.py:243-330, minus plots): the first --convert-count sorted utterances of
 --src_spk, each with a random utterance of --trg_spk (seeded by --seed), through `convert_mel`; the converted mels are
 voiced by the GPU Griffin-Lim inverse of the mel front-end (frontend.MelInverter, --griffin-lim-iters) instead of the
@@ -73,6 +75,12 @@ def get_parse():
     p.add_argument("--log-grad-norm", action="store_true", default=False,
                    help="measure the gradient norm and keep the non-finite guard without clipping (max_norm = inf); "
                         "scalars.jsonl gains the Grad/... keys either way")
+    p.add_argument("--ema-decay", type=float, default=0.0,
+                   help="keep an exponential moving average of the weights with this decay (0 < F < 1; warm-up "
+                        "min(F, (1 + k) / (10 + k))), on the device inside the step, and write it next to every checkpoint as "
+                        "<name>_<epoch>.ema.pth (0: off)")
+    p.add_argument("--use-ema", action="store_true", default=False,
+                   help="--convert: voice the averaged weights (<name>_<epoch>.ema.pth) instead of the last iterate")
     return p
 
 
@@ -196,7 +204,11 @@ def convert(vsc, args, logging_func=print):
     src, trg = args.src_spk, args.trg_spk
     save_dir = os.path.join(args.log_dir, "generation", f"{src}_to_{trg}")
     os.makedirs(save_dir, exist_ok=True)
-    vsc.load_last_model(os.path.join(args.log_dir, "checkpoints"), logging_func=logging_func)
+    try:
+        vsc.load_last_model(os.path.join(args.log_dir, "checkpoints"), logging_func=logging_func,
+                            use_ema=bool(getattr(args, "use_ema", False)))
+    except FileNotFoundError as e:
+        raise SystemExit(f"--use-ema: {e}")
     sources = sorted(glob(os.path.join(args.dataset_fp, src, "*.npy")))[:args.convert_count]
     targets = sorted(glob(os.path.join(args.dataset_fp, trg, "*.npy")))
     if not sources or not targets:
@@ -225,6 +237,8 @@ def convert(vsc, args, logging_func=print):
 
 def main(argv=None):
     args = get_parse().parse_args(argv)
+    if not 0.0 <= args.ema_decay < 1.0:
+        raise SystemExit(f"--ema-decay {args.ema_decay}: a decay with 0 < F < 1, or 0 for off")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         import sys
@@ -257,6 +271,8 @@ def main(argv=None):
         raise SystemExit(f"--clip-grad-norm {args.clip_grad_norm}: a positive norm, or 0 for off")
     if args.clip_grad_norm > 0 or args.log_grad_norm:
         vsc.optimizer.set_grad_clip(args.clip_grad_norm if args.clip_grad_norm > 0 else float("inf"))
+    if args.ema_decay > 0:
+        vsc.optimizer.set_ema(args.ema_decay)
     dp = world > 1 or os.environ.get("DVAE_FORCE_DDP", "0") == "1"
     if dp:
         setup_data_parallel(vsc, args.seed)

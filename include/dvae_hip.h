@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 313
+#define DVAE_ABI_VERSION 314
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -420,7 +420,33 @@ int dvae_adam_flat_dev_clip(float* p, float* g, float* m, float* v, int64_t n, f
                             float* state, const unsigned* skip_if_nonzero, const dvae_ranges_t* clear, int tick,
                             const float* clip, void* stream);
 
-/* x[0, n) = 0 (16-byte aligned): optimizer.zero_grad() (variational_base_vae.py:86) and the outputs that split-k
+/* ---- exponential moving average of the weights, on the device inside the (captured) step ----
+ * New functionality (the reference keeps the last iterate only).  Two launches after the Adam launch(es) of a full step:
+ * dvae_ema_tick: one small workgroup decides whether this step's update is applied and with what weight.  ema_state is
+ *   float[8], zero-initialised by the caller, [0] and [3] written by it — optim.FlatAdam.sync_scalars — outside any capture:
+ *     [0] decay, in [0, 1)
+ *     [1] k, the number of updates applied so far (a float: exact up to 2^24 updates)
+ *     [2] w = 1 - d_k, the weight of the last update
+ *     [3] warm-up: non-zero switches the ramp below on
+ *     [4] 1 while this step's update is applied, 0 while it is skipped
+ *     [5..7] reserved, never written
+ *   The step is skipped while *skip_if_nonzero != 0 (optional; the word dvae_adam_flat_dev gets) or, with clip_or_null given
+ *   (dvae_grad_clip_finalize's clip), while clip[4] != 0: [4] <- 0 and nothing else changes.  Otherwise k <- k + 1, [4] <- 1,
+ *     d = warm-up ? min(decay, (1 + k) / (10 + k)) : decay      in float64 from the float32 decay, with the NEW k
+ *     w = (float)(1.0 - d)                                      rounded once
+ *   (the first warm-up update has d = 2/11: the average follows the weights instead of holding on to the initial values).
+ * dvae_ema_update: while ema_state[4] != 0, ema[i] <- fmaf(w, p[i] - ema[i], ema[i]) with w = ema_state[2], for i in [0, n);
+ *   while ema_state[4] == 0 nothing is written.  p is only read.  n % 4 == 0, both pointers 16-byte aligned, the buffers do
+ *   not overlap; anything else is DVAE_EINVAL.  8 bytes read and 4 written per element, no atomics, no state shared between
+ *   workgroups: bit-identical from run to run.  An element with p[i] == ema[i] bit for bit keeps its bits (p - ema is +0
+ *   and w * 0 + ema is ema; the one exception is ema == p == -0.0, which becomes +0.0, and inf / NaN, which become NaN).
+ * dvae_swap_f32: a[i] <-> b[i] for i in [0, n), bits moved and never computed with; same rules for n, alignment and overlap.
+ *   optim.FlatAdam.swap_ema exchanges the weights and their average with it, in place: no temporary, no view changes. */
+int dvae_ema_tick(float* ema_state, const unsigned* skip_if_nonzero, const float* clip_or_null, void* stream);
+int dvae_ema_update(float* ema, const float* p, int64_t n, const float* ema_state, void* stream);
+int dvae_swap_f32(float* a, float* b, int64_t n, void* stream);
+
+/* x[0, n) = 0(16-byte aligned): optimizer.zero_grad() (variational_base_vae.py:86) and the outputs that split-k
  * contractions accumulate into atomically, zeroed by a launch of their own right in front of the accumulation. */
 int dvae_zero_f32(float* x, int64_t n, void* stream);
 
