@@ -61,7 +61,7 @@ COMPUTE_MODES = {"fp32": MODE_F32, "f32": MODE_F32, "float32": MODE_F32, "bf16":
                  "fp32x3": MODE_F32X3, "f32x3": MODE_F32X3}
 
 DEFAULT_COMPUTE_DTYPE = "fp32x3"
-ABI_VERSION = 314     # DVAE_ABI_VERSION of include/dvae_hip.h
+ABI_VERSION = 315     # DVAE_ABI_VERSION of include/dvae_hip.h
 
 # name -> (restype, argtypes); mirrors include/dvae_hip.h one to one
 SIGNATURES = {
@@ -164,6 +164,8 @@ SIGNATURES = {
     "dvae_dtw_batch_f0": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "dvae_softmax_ce": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, vp]),
     "dvae_scale_by": (i32, [vp, vp, vp, i64, vp]),
+    "dvae_pair_metrics": (i32, [vp] * 9 + [i32, i64, i32, i32, f32, f32, vp]),
+    "dvae_group_sum_f64": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "dvae_prof_enable": (i32, [i32]),
     "dvae_prof_collect": (i32, [C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]),
     "dvae_prof_collect_tags": (i32, [C.POINTER(C.c_uint), C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double),

@@ -14,7 +14,9 @@ preprocessing/encoder/utils.py:132-133) already resident on the device.
 from __future__ import annotations
 
 import glob
+import json
 import os
+import zlib
 from typing import Optional
 
 import numpy as np
@@ -23,15 +25,25 @@ from torch.utils.data import Dataset
 
 
 class SpeechDatasetGVAE(Dataset):
-    def __init__(self, file_path, sr=16000, samples_length=64, seed: Optional[int] = None):
+    def __init__(self, file_path, sr=16000, samples_length=64, seed: Optional[int] = None, exclude=None):
+        """exclude: files (paths as `split_corpus` returns them, or a dict speaker -> such paths) that never enter `spk_utt`:
+        the held-out part of the corpus.  `speaker_ids`, and with them the labels, stay those of the whole directory listing."""
         self.file_path = file_path
         self.sr = sr
         self.samples_length = samples_length
         self.rng = np.random.RandomState(seed) if seed is not None else np.random
-        self.speaker_ids = sorted(d for d in os.listdir(file_path) if os.path.isdir(os.path.join(file_path, d)))
+        self.speaker_ids = self.list_speakers(file_path)
         self.spk_utt = [np.array(sorted(glob.glob(os.path.join(file_path, s, "*.npy")))) for s in self.speaker_ids]
+        if exclude is not None:
+            out = {os.path.abspath(f) for f in _flat_files(exclude)}
+            self.spk_utt = [np.array([f for f in utt if os.path.abspath(f) not in out], dtype=utt.dtype)
+                            for utt in self.spk_utt]
         self.utterance_fp = np.empty((0, 2), dtype=object)
         self.shuffle_data()
+
+    @staticmethod
+    def list_speakers(file_path):
+        return sorted(d for d in os.listdir(file_path) if os.path.isdir(os.path.join(file_path, d)))
 
     def shuffle_data(self):
         pairs = []
@@ -61,6 +73,136 @@ class SpeechDatasetGVAE(Dataset):
 
     def get_utterance(self, speaker, utterance):
         return np.load(os.path.join(self.file_path, speaker, utterance))
+
+
+def _flat_files(held):
+    if isinstance(held, dict):
+        return [f for fs in held.values() for f in fs]
+    return list(held)
+
+
+# ------------------------------------------------------------------ the held-out split
+def split_corpus(root, val_fraction=0.0, val_speakers=(), seed=0):
+    """The held-out files of `<root>/<speaker>/*.npy`: dict speaker -> sorted list of paths (speakers with nothing held out
+    are left out).  The rule depends on the sorted speaker directories, the sorted file names and `seed` alone (not on the
+    training seed, not on the order a directory is listed in): per speaker the sorted files are permuted with
+    RandomState(seed ^ crc32(speaker)) and the first k are held out, k = floor(val_fraction n) rounded down to an even
+    number (validation pairs file i with file k/2 + i).  A speaker named in `val_speakers` is held out whole; an odd last
+    file of it is dropped from validation AND excluded from training (`excluded_files`)."""
+    return _split(root, val_fraction, val_speakers, seed)[0]
+
+
+def _split(root, val_fraction, val_speakers, seed):
+    val_fraction = float(val_fraction)
+    if not 0.0 <= val_fraction < 0.5:
+        raise ValueError(f"val_fraction {val_fraction}: expected 0 <= val_fraction < 0.5")
+    speakers = sorted(d for d in os.listdir(root) if os.path.isdir(os.path.join(root, d)))
+    val_speakers = tuple(val_speakers or ())
+    unknown = sorted(set(val_speakers) - set(speakers))
+    if unknown:
+        raise ValueError(f"val_speakers {unknown}: no such speaker directory under {root}")
+    held, dropped = {}, []
+    for spk in speakers:
+        files = sorted(glob.glob(os.path.join(root, spk, "*.npy")))
+        n = len(files)
+        if spk in val_speakers:
+            take = files[:n - (n & 1)]
+            dropped += files[n - (n & 1):]
+        else:
+            k = int(np.floor(val_fraction * n)) & ~1
+            rs = np.random.RandomState((int(seed) ^ zlib.crc32(spk.encode("utf-8"))) & 0xFFFFFFFF)
+            take = sorted(files[i] for i in rs.permutation(n)[:k])
+        if take:
+            held[spk] = take
+    return held, dropped
+
+
+def excluded_files(root, val_fraction=0.0, val_speakers=(), seed=0):
+    """What training must not see: the held-out files of `split_corpus` plus the odd last file of each `val_speakers`
+    speaker (dropped from validation, not trained on either)."""
+    held, dropped = _split(root, val_fraction, val_speakers, seed)
+    return _flat_files(held) + dropped
+
+
+def write_val_split(path, root, held, excluded, val_fraction, val_speakers, val_seed):
+    """`<log_dir>/val_split.json`: the held-out files relative to the corpus root, and the three settings that made them."""
+    rel = lambda f: os.path.relpath(f, root).replace(os.sep, "/")
+    rec = {"val_fraction": float(val_fraction), "val_speakers": sorted(val_speakers), "val_seed": int(val_seed),
+           "held_out": {spk: [rel(f) for f in fs] for spk, fs in held.items()},
+           "excluded": sorted(rel(f) for f in excluded)}
+    with open(path, "w") as fp:
+        json.dump(rec, fp, indent=1)
+    return rec
+
+
+def read_val_split(path, root, val_fraction, val_speakers, val_seed):
+    """-> (held, excluded) with absolute paths, from the file a first run wrote.  A resumed run whose flags disagree with it
+    would train on files the earlier epochs validated on: SystemExit, saying which setting differs."""
+    with open(path) as fp:
+        rec = json.load(fp)
+    want = {"val_fraction": float(val_fraction), "val_speakers": sorted(val_speakers), "val_seed": int(val_seed)}
+    diff = [f"{k}: {rec.get(k)!r} there, {v!r} now" for k, v in want.items() if rec.get(k) != v]
+    if diff:
+        raise SystemExit(f"{path} was written with another held-out split ({'; '.join(diff)}): a changed split would leak "
+                         "validation data into training.  Use the same --val-fraction / --val-speakers / --val-seed, or "
+                         "another --log_dir.")
+    full = lambda r: os.path.join(root, *r.split("/"))
+    return {spk: [full(r) for r in fs] for spk, fs in rec["held_out"].items()}, [full(r) for r in rec["excluded"]]
+
+
+class HeldOutPairs:
+    """The fixed pair list of a held-out split, resident on the device.  Per speaker the held-out files in sorted order,
+    file i paired with file k/2 + i; never shuffled.  The crop is centred (start (L - T) // 2 when L > T; otherwise start 0
+    and zeros on the right, the dataset's rule), made by the gather kernel of GpuPairLoader from mels uploaded once.
+    `batches(batch_size)` yields (x1, x2, speaker index int32 on the device); the last batch may be short, no pair is
+    dropped.  device=None builds the lists only (pairs, offsets, speakers) and uploads nothing."""
+
+    def __init__(self, held, samples_length, speaker_ids, device="cuda"):
+        self.T = int(samples_length)
+        self.speaker_ids = list(speaker_ids)
+        self.pairs, spk = [], []
+        for name in sorted(held):
+            files = sorted(held[name])
+            half = len(files) // 2
+            self.pairs += [(files[i], files[half + i]) for i in range(half)]
+            spk += [self.speaker_ids.index(name)] * half
+        self.speakers = np.array(spk, dtype=np.int32)
+        files = sorted({f for p in self.pairs for f in p})
+        self.index = {f: i for i, f in enumerate(files)}
+        arrs = [np.load(f) for f in files]
+        self.lengths = np.array([a.shape[1] for a in arrs], dtype=np.int32)
+        self.offsets = np.array([(int(L) - self.T) // 2 if L > self.T else 0 for L in self.lengths], dtype=np.int32)
+        self.u1 = np.array([self.index[a] for a, _ in self.pairs], dtype=np.int32)
+        self.u2 = np.array([self.index[b] for _, b in self.pairs], dtype=np.int32)
+        self.device = None if device is None else torch.device(device)
+        if self.device is None or not arrs:
+            return
+        self.C, self.Lmax = arrs[0].shape[0], int(self.lengths.max())
+        host = np.zeros((len(arrs), self.C, self.Lmax), dtype=np.float32)
+        for i, a in enumerate(arrs):
+            host[i, :, :a.shape[1]] = a
+        self.mels = torch.from_numpy(host).to(self.device)
+        self.lens_dev = torch.from_numpy(self.lengths).to(self.device)
+        self.spk_dev = torch.from_numpy(self.speakers).to(self.device)
+
+    def __len__(self):
+        return len(self.pairs)
+
+    def _gather(self, utt):
+        from ._lib import check, lib, ptr, stream
+        u = torch.from_numpy(np.ascontiguousarray(utt)).to(self.device)
+        o = torch.from_numpy(np.ascontiguousarray(self.offsets[utt])).to(self.device)
+        out = torch.empty((len(utt), self.C, self.T), device=self.device, dtype=torch.float32)
+        check(lib().dvae_gather_crop(ptr(self.mels), ptr(self.lens_dev), ptr(u), ptr(o), ptr(out), len(utt), self.C, self.T,
+                                     self.Lmax, stream()), "dvae_gather_crop")
+        return out
+
+    def batches(self, batch_size):
+        if self.device is None:
+            raise RuntimeError("HeldOutPairs(device=None) holds the pair list only")
+        for lo in range(0, len(self.pairs), int(batch_size)):
+            hi = min(lo + int(batch_size), len(self.pairs))
+            yield self._gather(self.u1[lo:hi]), self._gather(self.u2[lo:hi]), self.spk_dev[lo:hi]
 
 
 def write_synthetic_corpus(root, n_speakers=2, n_utt=8, n_mel=80, length=96, seed=0):

@@ -412,11 +412,13 @@ class DisentangledVAE(nn.Module):
         eps_c = torch.randn((2 * Bh, Cn), device=dev, dtype=torch.float32) if train else None
         return eps_c, torch.randn((Bh, S), device=dev, dtype=torch.float32)
 
-    def forward_full(self, x1, x2, train=True):
+    def forward_full(self, x1, x2, train=True, eps_style=None):
         """The forward pass with its outputs UNSPLIT: (rec, rec_hat, q_mu, q_lv, s_mu, s_lv) with rec / rec_hat [2*Bh, 80, T]
         and q_mu / q_lv [2*Bh, Cn] holding the x1 half first.  `forward` returns the reference's ten tensors as views of
         these; the training step hands the unsplit tensors to the fused loss (ops.LossGVAE2FullFn), so that autograd
-        has no slice to undo (each `t[:Bh]` costs a zero-fill and a copy in backward)."""
+        has no slice to undo (each `t[:Bh]` costs a zero-fill and a copy in backward).
+        eps_style (train=False only): the style noise [Bh, S] of the inference pass, which the reference samples in eval
+        too (:261) — given, no generator is touched (the validation pass draws it from a generator of its own)."""
         self._check(x1)
         self._check(x2)
         self._refresh_derived()
@@ -426,7 +428,12 @@ class DisentangledVAE(nn.Module):
         # [T*N, 80]; bf16 in the bf16 compute mode (it only feeds the first conv)
         x = mel_to_frames(x1.contiguous(), x2.contiguous(), dtype=ops.act_storage(ops.current_mode()))
         style, content = self._encode_frames(x, T, N, 2)
-        eps_c, eps_s = self._eps(Bh, x1.device, train)
+        if eps_style is None:
+            eps_c, eps_s = self._eps(Bh, x1.device, train)
+        elif train or tuple(eps_style.shape) != (Bh, S):
+            raise ValueError(f"forward_full: eps_style is the [{Bh}, {S}] style noise of a train=False pass")
+        else:
+            eps_c, eps_s = None, eps_style.to(x1.device, torch.float32).contiguous()
         z, q_mu, q_lv, s_mu, s_lv = LatentFn.apply(style, content, eps_c, eps_s, Bh, S, Cn)
         y = self._decode_frames(z, T, N, 2)                              # [T*N, 80]
         y, y_res, y_in = fanout(y, 3)       # loss, residual and postnet input: one gradient sum (ops.FanoutFn)

@@ -329,6 +329,94 @@ class VariationalBaseModelVAE:
         # NB the reference returns the style KL of the LAST batch, not the total (:101)
         return tot[1], tot[2], tot[3], tot[4], tot[5], tot[6], last_style
 
+    # ---- variational_base_vae.py:105-123 (test), per pair and per speaker
+    VAL_TERMS = ("Loss", "Reconstruction Loss1", "Reconstruction Loss2", "Reconstruction Loss1 hat",
+                 "Reconstruction Loss2 hat", "Z1 KL Loss", "Z2 KL Loss", "Z KL Style")
+    val_seed = 0            # seed of the validation pass's private style-noise generator
+    val_batch_size = None   # pairs per validation batch (None: the configured batch size)
+
+    def validate(self, val_pairs, logging_func=print, use_ema=False):
+        """The eight loss terms on a held-out pair list (data.HeldOutPairs, or anything with `batches(batch_size)` yielding
+        (x1, x2, int32 speaker index) and `speaker_ids`): eval-mode forward (`train=False`: content z = mu, BatchNorm on
+        running statistics, the style sampled as the reference does in eval), per-pair terms (ops.pair_metrics: the
+        reference's formulas with batch_size 1), float64 sums per speaker over all batches (ops.group_sum), ONE
+        device->host copy.  `len(val_pairs)` is the number of pairs.  Means are per PAIR: independent of the batching, and on a full batch exactly what the training
+        scalars report.  The style noise comes from a private generator re-seeded with `val_seed` at the start of every
+        pass — the same noise every epoch and for both weight sets — so the default generator, and with it every later
+        training step, is left alone; so are weights, moments, BatchNorm buffers and the loaders' streams.
+        use_ema: run on the averaged weights (keys `Val EMA/...`); the live weights and their derived layouts are back
+        afterwards."""
+        from .. import ops
+        m = self.model
+        names = list(val_pairs.speaker_ids)
+        G, prefix = len(names), "Val EMA/" if use_ema else "Val/"
+        dev = torch.device(self.device)
+        S = m.speaker_size
+        gen = getattr(self, "_val_gen", None)
+        if gen is None or gen.device != dev:
+            gen = self._val_gen = torch.Generator(device=dev)
+        gen.manual_seed(int(self.val_seed))
+        sums = torch.zeros((G + 1, 8), dtype=torch.float64, device=dev)
+        counts = torch.zeros(2 * (G + 1), dtype=torch.int64, device=dev)       # counts | bad
+        self.val_rows = rows_all = []                                           # per-pair rows of the pass, on the device
+        was_training = m.training
+        m.eval()
+        try:
+            with torch.no_grad():
+                if use_ema:
+                    self.optimizer.swap_ema()
+                try:
+                    # the pass's style noise, one row per pair in list order: a pair's noise does not depend on its batch
+                    eps_all = torch.randn((len(val_pairs), S), device=dev, dtype=torch.float32, generator=gen)
+                    Bc, done = int(self.batch_size), [0]
+
+                    def launch(a, b, spk):
+                        n = a.shape[0]
+                        eps = eps_all[done[0]:done[0] + n]
+                        if n < Bc:
+                            pad = lambda t: torch.cat([t, t.new_zeros((Bc - n,) + tuple(t.shape[1:]))])
+                            a, b, eps = pad(a), pad(b), pad(eps)
+                        outs = m.forward_full(a.contiguous(), b.contiguous(), train=False, eps_style=eps.contiguous())
+                        rows = ops.pair_metrics(a, b, *outs, self.mse_cof, self.kl_cof)[:n]
+                        ops.group_sum(rows, spk.contiguous(), sums, counts[:G + 1], counts[G + 1:])
+                        rows_all.append(rows)
+                        done[0] += n
+
+                    # The launches are a function of the pair LIST, not of how the caller batched it: pair i is row i % B of
+                    # forward i // B at the training step's shape (B the configured batch size; the last one padded with
+                    # silent pairs whose rows are dropped).  The contraction kernels pick tiles and splits by shape, and the
+                    # W_hh-resident H = 1024 recurrence adds its four k-quarters in an order that turns with the row
+                    # (csrc/lstm_pers.hip, lstm_pers_fwd_x3: the owner wave of rows 4q + {0, 1} is not that of 4q + {2, 3}), so
+                    # a pair's last bits depend on its shape AND its row; fixing both makes them independent of the batching.
+                    held = None
+                    for piece in val_pairs.batches(self.val_batch_size or Bc):
+                        held = piece if held is None else tuple(torch.cat([h, p]) for h, p in zip(held, piece))
+                        while held[0].shape[0] >= Bc:
+                            launch(*(t[:Bc] for t in held))
+                            held = tuple(t[Bc:] for t in held)
+                    if held is not None and held[0].shape[0]:
+                        launch(*held)
+                finally:
+                    if use_ema:
+                        self.optimizer.swap_ema()
+                        m._refresh_derived()        # packed transposes / bf16 copies: those of the live weights again
+        finally:
+            m.train(was_training)
+        packed = torch.cat([sums.view(-1), counts.double()]).tolist()           # the pass's one copy (counts < 2^53)
+        self._check_device_errors()
+        tab, cnt, bad = packed[:8 * (G + 1)], packed[8 * (G + 1):9 * (G + 1)], packed[9 * (G + 1):]
+        mean = lambda g: [tab[8 * g + k] / cnt[g] if cnt[g] else float("nan") for k in range(8)]
+        res = {prefix + t: v for t, v in zip(self.VAL_TERMS, mean(G))}
+        res[prefix + "Pairs"], res[prefix + "Non-finite pairs"] = int(cnt[G]), int(bad[G])
+        res["per_speaker"] = {name: dict(zip(self.VAL_TERMS, mean(g)), **{"Pairs": int(cnt[g]), "Non-finite pairs": int(bad[g])})
+                              for g, name in enumerate(names) if cnt[g] or bad[g]}
+        logging_func("====> {}set loss: {:.4f} ({} pairs)".format(prefix.replace("/", " "), res[prefix + "Loss"], int(cnt[G])))
+        return res
+
+    def test(self, test_loader, epoch, logging_func=print):
+        """The reference's test() (:105-123): the held-out loss of this epoch, per pair."""
+        return self.validate(test_loader, logging_func)["Val/Loss"]
+
     # ---- variational_base_vae.py:127-149
     def load_last_model(self, checkpoints_path, logging_func=print, use_ema=False):
         """use_ema: take the weights from `<base>.ema.pth` (the averaged weights run_training writes next to `<base>.pth`
@@ -452,13 +540,40 @@ class VariationalBaseModelVAE:
         finally:
             m.train(was_training)
 
+    @staticmethod
+    def _note_best(checkpoints_path, base, epoch, val):
+        """`best.json` names the checkpoint with the lowest Val/Loss seen at any checkpoint so far (an existing file counts:
+        a resumed run).  Candidates of this epoch: the last iterate and, if written, the average.  Not a .pth:
+        load_last_model never sees it."""
+        import math
+        path = os.path.join(checkpoints_path, "best.json")
+        cands = [(val["last"]["Val/Loss"], base + ".pth", False)]
+        if "ema" in val and os.path.exists(os.path.join(checkpoints_path, base + ".ema.pth")):
+            cands.append((val["ema"]["Val EMA/Loss"], base + ".ema.pth", True))
+        cands = [c for c in cands if math.isfinite(c[0])]
+        if not cands:
+            return
+        loss, name, ema = min(cands, key=lambda c: c[0])
+        if os.path.exists(path):
+            with open(path) as fp:
+                old = json.load(fp)
+            if old.get("Val/Loss") is not None and old["Val/Loss"] <= loss and \
+                    os.path.exists(os.path.join(checkpoints_path, old.get("weights", ""))):
+                return
+        with open(path, "w") as fp:
+            json.dump({"epoch": epoch, "weights": name, "Val/Loss": loss, "ema": ema}, fp)
+
     def _is_rank0(self):
         return self.reducer is None or self.reducer.rank == 0
 
     # ---- variational_base_vae.py:156-202
     def run_training(self, train_loader, test_loader, epochs, report_interval, sample_sz=64, reload_model=True,
                      checkpoints_path="", logs_path="", images_path="", estimation_dir="", logging_func=print,
-                     start_epoch=None):
+                     start_epoch=None, val_pairs=None, val_interval=1):
+        """val_pairs (data.HeldOutPairs; None: no validation, nothing below happens): every `val_interval` epochs and at every
+        checkpoint epoch rank 0 runs `validate` — on the average too while FlatAdam.set_ema is on — its numbers join the
+        epoch's record, `val.json` beside `logs_path` (the command line's <log_dir>) holds the per-speaker table of the last pass, and the checkpoint with the
+        lowest `Val/Loss` so far (last iterate or average) is named by `<checkpoints_path>/best.json`."""
         start_epoch = self.load_last_model(checkpoints_path, logging_func) if reload_model else 1
         run_name = "DisentangledVAE_VCTK"
         log_f = None
@@ -476,6 +591,20 @@ class VariationalBaseModelVAE:
                 rec.update(self.grad_stats)
             if getattr(self, "ema_stats", None):        # weight average on (FlatAdam.set_ema)
                 rec.update(self.ema_stats)
+            ckpt_epoch = epoch % report_interval == 0 and bool(checkpoints_path)
+            val = None
+            if val_pairs is not None and self._is_rank0() and (epoch % max(1, int(val_interval)) == 0 or ckpt_epoch):
+                quiet = lambda *_: None
+                val = {"epoch": epoch, "last": self.validate(val_pairs, quiet)}
+                if getattr(self.optimizer, "ema_decay", None) is not None:
+                    val["ema"] = self.validate(val_pairs, quiet, use_ema=True)
+                for res in (val["last"], val.get("ema", {})):
+                    rec.update({k: v for k, v in res.items() if k != "per_speaker"})
+                if logs_path:
+                    # beside the logs directory: the command line's <log_dir>/val.json
+                    with open(os.path.join(os.path.dirname(os.path.normpath(logs_path)), "val.json"), "w") as fp:
+                        json.dump({"epoch": epoch, "per_speaker": val["last"]["per_speaker"],
+                                   **({"per_speaker_ema": val["ema"]["per_speaker"]} if "ema" in val else {})}, fp, indent=1)
             history.append(rec)
             if self._is_rank0():
                 logging_func(json.dumps(rec))
@@ -500,6 +629,8 @@ class VariationalBaseModelVAE:
                         # running statistics) are the same tensors in both files
                         with self.ema_weights():
                             torch.save(self.model.state_dict(), base + ".ema.pth")
+                if val is not None:
+                    self._note_best(checkpoints_path, f"{run_name}_{epoch}", epoch, val)
                 # variational_base_vae.py:196-201: reconstructions of one test batch from the checkpoint just written
                 if estimation_dir and test_loader is not None:
                     self.estimate_trained_model(test_loader, checkpoints_path, estimation_dir)

@@ -1539,6 +1539,43 @@ def softmax_ce_eval(logits, labels, classes=None):
     return softmax_ce(logits.detach(), labels, classes)[2][:3]
 
 
+# ----------------------------------------------------------------------------- held-out validation (csrc/val.hip)
+def pair_metrics(x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv, mse_cof, kl_cof, out=None):
+    """dvae_pair_metrics on the unsplit outputs of `DisentangledVAE.forward_full`: the eight loss terms of every pair,
+    out [Bh, 8] fp32 in the order of the training step's loss vector (no gradient, no host sync)."""
+    ts = [t.detach() for t in (x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv)]
+    _ok(*ts)
+    x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv = ts
+    Bh = x1.shape[0]
+    n_per = x1.numel() // max(1, Bh)
+    D, S = q_mu.shape[-1], s_mu.shape[-1]
+    if not (x2.shape == x1.shape and rec.numel() == rec_hat.numel() == 2 * Bh * n_per and q_mu.shape == q_lv.shape == (2 * Bh, D)
+            and s_mu.shape == s_lv.shape == (Bh, S)):
+        raise ValueError("pair_metrics: expected x1, x2 [Bh, ...], rec, rec_hat [2 Bh, ...], q_mu, q_lv [2 Bh, D], s_mu, s_lv [Bh, S]")
+    if out is None:
+        out = torch.empty((Bh, 8), device=x1.device, dtype=torch.float32)
+    check(lib().dvae_pair_metrics(ptr(x1), ptr(x2), ptr(rec), ptr(rec_hat), ptr(q_mu), ptr(q_lv), ptr(s_mu), ptr(s_lv),
+                                  ptr(out), Bh, n_per, D, S, float(mse_cof), float(kl_cof), stream()), "dvae_pair_metrics")
+    return out
+
+
+def group_sum(rows, group, sums, counts, bad):
+    """dvae_group_sum_f64: rows [P, K] fp32 and their int32 groups are ADDED to sums [G + 1, K] float64, counts [G + 1] and
+    bad [G + 1] int64 (row G: the total) — sequential float64 sums in row order, no atomics."""
+    _ok(rows)
+    G, K = sums.shape[0] - 1, sums.shape[1]
+    P = rows.shape[0]
+    if not (rows.dim() == 2 and rows.shape[1] == K and group.is_cuda and group.dtype == torch.int32 and group.is_contiguous()
+            and group.numel() == P):
+        raise ValueError("group_sum: rows [P, K] fp32 with one contiguous int32 GPU group per row")
+    for t, dt, n in ((sums, torch.float64, (G + 1) * K), (counts, torch.int64, G + 1), (bad, torch.int64, G + 1)):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() == n):
+            raise ValueError("group_sum: sums [G + 1, K] float64, counts and bad [G + 1] int64, contiguous on the GPU")
+    check(lib().dvae_group_sum_f64(ptr(rows), ptr(group), P, K, G, ptr(sums), ptr(counts), ptr(bad), stream()),
+          "dvae_group_sum_f64")
+    return sums, counts, bad
+
+
 class SoftmaxCeFn(torch.autograd.Function):
     """F.cross_entropy(logits[:, :classes], labels, ignore_index=<any negative>) as ONE pass over the logits: the mean
     loss over the counted rows (a device scalar), with the gradient of the logits left behind pre-scaled by 1 / count.

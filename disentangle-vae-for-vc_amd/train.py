@@ -9,6 +9,10 @@ train.py:53).  Parsed-and-ignored flags of the reference (--hidden-size --alpha 
 --sample-size --no-cuda --do-not-resume --log-interval) are accepted for command-line compatibility.
 --ema-decay F (new): an exponential moving average of the weights, kept on the device inside the step (optim.FlatAdam.set_ema)
 and written as <name>_<epoch>.ema.pth next to every checkpoint; --use-ema makes --convert voice it.
+--val-fraction F / --val-speakers a,b (new): a held-out part of the corpus that training never sees (data.split_corpus, fixed by
+--val-seed and written to <log_dir>/val_split.json), the eight loss terms on it every --val-interval epochs (last iterate and,
+with --ema-decay, the average: Val/... and Val EMA/... in scalars.jsonl, per speaker in <log_dir>/val.json) and
+checkpoints/best.json naming the checkpoint with the lowest Val/Loss; --use-best makes --convert voice that one.
 --convert (reference variational_base_vae.py:243-330, minus plots): the first --convert-count sorted utterances of
 --src_spk, each with a random utterance of --trg_spk (seeded by --seed), through `convert_mel`; the converted mels are
 voiced by the GPU Griffin-Lim inverse of the mel front-end (frontend.MelInverter, --griffin-lim-iters) instead of the
@@ -81,12 +85,20 @@ def get_parse():
                         "<name>_<epoch>.ema.pth (0: off)")
     p.add_argument("--use-ema", action="store_true", default=False,
                    help="--convert: voice the averaged weights (<name>_<epoch>.ema.pth) instead of the last iterate")
+    p.add_argument("--val-fraction", type=float, default=0.0,
+                   help="hold this fraction of every speaker's utterances out of training (0 <= F < 0.5) and report the "
+                        "loss terms on them every --val-interval epochs (0: off)")
+    p.add_argument("--val-speakers", type=str, default="", help="comma-separated speakers held out whole")
+    p.add_argument("--val-seed", type=int, default=0, help="seed of the split and of the validation pass's style noise")
+    p.add_argument("--val-interval", type=int, default=1, help="validate every N epochs (and at every checkpoint)")
+    p.add_argument("--use-best", action="store_true", default=False,
+                   help="--convert: voice the checkpoint that checkpoints/best.json names (lowest Val/Loss)")
     return p
 
 
-def get_dataset(dataset_fp, batch_size, samples_length=64, seed=None):
+def get_dataset(dataset_fp, batch_size, samples_length=64, seed=None, exclude=None):
     from .data import SpeechDatasetGVAE
-    ds = SpeechDatasetGVAE(dataset_fp, samples_length=samples_length, seed=seed)
+    ds = SpeechDatasetGVAE(dataset_fp, samples_length=samples_length, seed=seed, exclude=exclude)
     # drop_last keeps the batch shape fixed (hipGraph replay); the reference uses drop_last=False (train.py:55-56)
     return DataLoader(ds, batch_size=batch_size, pin_memory=True, shuffle=True, drop_last=True), ds
 
@@ -194,6 +206,45 @@ def write_wav(path: str, wav, sample_rate: int = 16000):
         w.writeframes(pcm.tobytes())
 
 
+def load_best(vsc, checkpoints_path, logging_func=print):
+    """--use-best: the weights that <checkpoints>/best.json names (run_training writes it while validation is on)."""
+    path = os.path.join(checkpoints_path, "best.json")
+    if not os.path.exists(path):
+        raise SystemExit(f"--use-best: {path} is missing (train with --val-fraction / --val-speakers)")
+    with open(path) as fp:
+        best = json.load(fp)
+    weights = os.path.join(checkpoints_path, best["weights"])
+    if not os.path.exists(weights):
+        raise SystemExit(f"--use-best: {path} names {best['weights']}, which is missing")
+    vsc.model.load_state_dict(torch.load(weights, map_location=vsc.device))
+    logging_func(f"Loading the best checkpoint {best['weights']} (epoch {best['epoch']}, Val/Loss {best['Val/Loss']:.4f})...")
+    return best
+
+
+def held_out_split(args, rank=0):
+    """(held, excluded) of --val-fraction / --val-speakers, or (None, None) when neither is given.  The first run writes
+    <log_dir>/val_split.json; a later run on the same <log_dir> reads it, and exits if its flags ask for another split."""
+    from .data import excluded_files, read_val_split, split_corpus, write_val_split
+    speakers = tuple(s for s in args.val_speakers.split(",") if s)
+    path = os.path.join(args.log_dir, "val_split.json")
+    # (the other ranks of a data-parallel run compute the same split from the same flags: rank 0 may still be writing)
+    if rank == 0 and os.path.exists(path) and not args.do_not_resume:
+        return read_val_split(path, args.dataset_fp, args.val_fraction, speakers, args.val_seed)
+    if args.val_fraction == 0.0 and not speakers:
+        return None, None
+    try:
+        held = split_corpus(args.dataset_fp, args.val_fraction, speakers, args.val_seed)
+        excluded = excluded_files(args.dataset_fp, args.val_fraction, speakers, args.val_seed)
+    except ValueError as e:
+        raise SystemExit(f"--val-fraction / --val-speakers: {e}")
+    if not held:
+        raise SystemExit("--val-fraction / --val-speakers: nothing is held out (two files per speaker at the least)")
+    if rank == 0:
+        os.makedirs(args.log_dir, exist_ok=True)
+        write_val_split(path, args.dataset_fp, held, excluded, args.val_fraction, speakers, args.val_seed)
+    return held, excluded
+
+
 def convert(vsc, args, logging_func=print):
     """--convert: reference voice_conversion_mel (variational_base_vae.py:243-330) with the Griffin-Lim vocoder"""
     from glob import glob
@@ -204,11 +255,14 @@ def convert(vsc, args, logging_func=print):
     src, trg = args.src_spk, args.trg_spk
     save_dir = os.path.join(args.log_dir, "generation", f"{src}_to_{trg}")
     os.makedirs(save_dir, exist_ok=True)
-    try:
-        vsc.load_last_model(os.path.join(args.log_dir, "checkpoints"), logging_func=logging_func,
-                            use_ema=bool(getattr(args, "use_ema", False)))
-    except FileNotFoundError as e:
-        raise SystemExit(f"--use-ema: {e}")
+    if getattr(args, "use_best", False):
+        load_best(vsc, os.path.join(args.log_dir, "checkpoints"), logging_func)
+    else:
+        try:
+            vsc.load_last_model(os.path.join(args.log_dir, "checkpoints"), logging_func=logging_func,
+                                use_ema=bool(getattr(args, "use_ema", False)))
+        except FileNotFoundError as e:
+            raise SystemExit(f"--use-ema: {e}")
     sources = sorted(glob(os.path.join(args.dataset_fp, src, "*.npy")))[:args.convert_count]
     targets = sorted(glob(os.path.join(args.dataset_fp, trg, "*.npy")))
     if not sources or not targets:
@@ -261,8 +315,13 @@ def main(argv=None):
     torch.cuda.manual_seed(args.seed + 7919 * rank)      # every rank its own reparameterisation-noise stream
     if rank == 0:
         os.makedirs(args.log_dir, exist_ok=True)
+        cfg = dict(vars(args))
+        val_keys = ("val_fraction", "val_speakers", "val_seed", "val_interval", "use_best")
+        if all(cfg[k] == get_parse().get_default(k) for k in val_keys):
+            for k in val_keys:      # none of the validation flags given: the file a run wrote before they existed
+                del cfg[k]
         with open(os.path.join(args.log_dir, "config.json"), "w") as fp:
-            json.dump(vars(args), fp, indent=4)
+            json.dump(cfg, fp, indent=4)
     vsc = ConvolutionalMulVAE(args.dataset, args.samples_length, 80, args.latent_size, args.lr, args.alpha,
                               args.log_interval, args.normalize, speaker_size=args.speaker_size, device=device,
                               latent_dim=args.latent_size, beta=args.beta_cof, batch_size=args.batch_size,
@@ -277,14 +336,22 @@ def main(argv=None):
     if dp:
         setup_data_parallel(vsc, args.seed)
     use_gpu_loader = args.gpu_loader == 1 or (args.gpu_loader < 0 and dp)
+    held, excluded = held_out_split(args, rank) if args.train else (None, None)
+    val_kw = {}
+    if held is not None:
+        vsc.val_seed = args.val_seed
+        if rank == 0:       # only rank 0 validates, as only rank 0 runs estimate_trained_model
+            from .data import HeldOutPairs, SpeechDatasetGVAE as _DS
+            ids = _DS.list_speakers(args.dataset_fp)
+            val_kw = {"val_pairs": HeldOutPairs(held, args.samples_length, ids, device), "val_interval": args.val_interval}
     if use_gpu_loader:
         from .data import GpuPairLoader, SpeechDatasetGVAE
-        ds = SpeechDatasetGVAE(args.dataset_fp, samples_length=args.samples_length, seed=args.seed)
+        ds = SpeechDatasetGVAE(args.dataset_fp, samples_length=args.samples_length, seed=args.seed, exclude=excluded)
         loader = GpuPairLoader(ds, args.batch_size, device=device, seed=args.seed, rank=rank, world_size=world)
     else:
         if world > 1:
             raise SystemExit("--gpu-loader 0 has no sharding: data-parallel runs feed from data.GpuPairLoader")
-        loader, _ = get_dataset(args.dataset_fp, args.batch_size, args.samples_length, seed=args.seed)
+        loader, _ = get_dataset(args.dataset_fp, args.batch_size, args.samples_length, seed=args.seed, exclude=excluded)
     if args.graph:
         vsc.enable_graph(True)     # with a reducer attached the step still runs eagerly unless DVAE_DDP_GRAPH=1
     hist = None
@@ -299,7 +366,7 @@ def main(argv=None):
                                     checkpoints_path=os.path.join(args.log_dir, "checkpoints"),
                                     images_path=os.path.join(args.log_dir, "images"),
                                     logs_path=os.path.join(args.log_dir, "logs"),
-                                    estimation_dir=os.path.join(args.log_dir, "images", "estimation"))
+                                    estimation_dir=os.path.join(args.log_dir, "images", "estimation"), **val_kw)
         if args.convert and rank == 0:
             convert(vsc, args)
     except BaseException:

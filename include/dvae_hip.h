@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 314
+#define DVAE_ABI_VERSION 315
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -647,6 +647,32 @@ int dvae_dtw_batch_f0(const float* x, const float* y, const float* lf0x, const f
 int dvae_softmax_ce(const float* logits, const int* labels, float* dlogits, float* row_loss, int* row_pred, float* out,
                     int rows, int classes, int64_t ld, float grad_scale, void* stream);
 int dvae_scale_by(const float* x, const float* scale, float* y, int64_t n, void* stream);
+
+/* ---- held-out validation (model/variational_base_vae.py: validate) ----
+ * The reference's test() (variational_base_vae.py:105-123) sums loss_functionGVAE2 (disentangled_vae.py:310-327) over the
+ * test batches.  dvae_pair_metrics gives those eight terms PER PAIR: the reference's formulas with its batch_size set to 1,
+ * so that the mean of the rows of a full batch is what dvae_loss_fwd reports for it, and a held-out set gives the same
+ * numbers however it was batched (a ragged last batch included).  Layouts of DisentangledVAE.forward_full:
+ *   x1, x2 [Bh, n_per]; rec, rec_hat [2 Bh, n_per] (x1 half first); q_mu, q_lv [2 Bh, D]; s_mu, s_lv [Bh, S]; out [Bh, 8]:
+ *   out[b] = (LOSS, L1(x1[b], rec[b]), L1(x2[b], rec[Bh+b]), the same two on rec_hat, KL_1, KL_2, KL_style) with
+ *   L1 = sum|x - r|, KL_1 / KL_2 = -0.5 sum_d(1 + lv - mu^2 - exp lv) over rows b / Bh + b of q_*, KL_style = -sum_s(...) over
+ *   row b of s_*, LOSS = mse_cof (((L1_1 + L1_2) + L1_1hat) + L1_2hat) + kl_cof (KL_1 + KL_2).
+ *   One workgroup of 256 threads per pair; float4 loads when x1, x2, rec, rec_hat are 16-byte aligned and n_per % 4 == 0,
+ *   a scalar walk otherwise; any n_per, D, S >= 1.  The elementwise terms are fp32, as dvae_loss_fwd computes them; every
+ *   accumulation is float64 in a fixed order (per thread, then a fixed tree), LOSS is combined in float64 from the unrounded
+ *   sums, and each output rounds once, at the store.  No atomics: two launches give the same bits.
+ * dvae_group_sum_f64: rows [P, K] fp32 (K <= 256), group [P] int32; sums [G + 1, K] float64, counts [G + 1], bad [G + 1] int64 are
+ *   ACCUMULATED INTO (one set of buffers spans all batches of a pass; the caller zeroes them first); row G is the total.
+ *   Row p counts when 0 <= group[p] < G and its K values are all finite: it is added to sums[group[p]] and sums[G], and
+ *   counts[group[p]], counts[G] grow by one.  Otherwise it enters no sum: a row with a value that is not finite adds one to
+ *   bad[group[p]] and to bad[G], a row whose group is out of range to bad[G] alone.  One workgroup per output row, thread k
+ *   walks p = 0 ... P - 1 in order: each sums[g][k] equals, in every bit, the sequential float64 sum (old value first).
+ * Null pointers or sizes < 1 return DVAE_EINVAL and launch nothing. */
+int dvae_pair_metrics(const float* x1, const float* x2, const float* rec, const float* rec_hat, const float* q_mu,
+                      const float* q_lv, const float* s_mu, const float* s_lv, float* out, int Bh, int64_t n_per, int D,
+                      int S, float mse_cof, float kl_cof, void* stream);
+int dvae_group_sum_f64(const float* rows, const int* group, int P, int K, int G, double* sums, int64_t* counts, int64_t* bad,
+                       void* stream);
 
 /* ---- opt-in per-family kernel timing with HIP events on the launch stream (bench.py roofline) ----
  * family: 0 = off, 1 = GEMM/conv contraction kernel, 2 = LSTM step kernels.
