@@ -819,7 +819,7 @@ DVAE_API int dvae_stft_magnitude(const float* reim, float* mag, int64_t rows, in
 
 DVAE_API int dvae_mel_db_normalize(const float* mel, float* out, int M, int n_mels, int64_t ld_out, int64_t col0,
                                    float min_level, float ref_level_db, float min_level_db, void* stream) {
-  if (!mel || !out || M < 1 || n_mels < 1 || ld_out < M || col0 < 0 || !(min_level > 0.f) || !(min_level_db < 0.f))
+  if (!mel || !out || M < 1 || n_mels < 1 || col0 < 0 || ld_out < col0 + M || !(min_level > 0.f) || !(min_level_db < 0.f))
     return DVAE_EINVAL;
   dim3 grid((M + 31) / 32, (n_mels + 31) / 32);
   hipLaunchKernelGGL(mel_db_normalize_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel, out + col0,

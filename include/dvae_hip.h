@@ -500,7 +500,8 @@ int dvae_mul_div(const float* a, const float* b, const float* c, float* out, int
  * The two contractions (frames x DFT basis, magnitudes x mel basis) are dvae_gemm_f32 launches; these are the passes around them.
  * dvae_stft_frames: frames[M, fsize] = window * signal zero-padded by `left` samples in front (lws pads fsize-hop, :82-103).
  * dvae_stft_magnitude: reim[rows, 2*nbp] (real block | imaginary block) -> mag[rows, nbp].
- * dvae_mel_db_normalize: mel[M, n_mels] (frame-major) -> out[n_mels, ld_out] at column col0 (the [80, L] layout of the .npy corpus). */
+ * dvae_mel_db_normalize: mel[M, n_mels] (frame-major) -> out[n_mels, ld_out] at column col0 (the [80, L] layout of the .npy corpus);
+ *   DVAE_EINVAL unless col0 >= 0 and col0 + M <= ld_out (the M columns must fit inside a row of out). */
 int dvae_stft_frames(const float* wav, int64_t n, const float* window, float* frames, int M, int fsize, int hop,
                      int left, void* stream);
 int dvae_stft_magnitude(const float* reim, float* mag, int64_t rows, int nbins_padded, void* stream);
