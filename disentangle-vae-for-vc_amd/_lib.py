@@ -180,8 +180,6 @@ DEV_SIGNATURES = {
     "dvae_probe_mfma_bf16": (i32, [i32, i32, i32, vp, vp, vp]),
     "dvae_probe_coissue": (i32, [i32, i32, i32, i32, vp, vp, vp]),
     "dvae_lstm_pers_set_ts": (i32, [vp, i32]),
-    "dvae_lstm_pers_set_dbg": (i32, [vp, vp, i32, i32]),
-    "dvae_lstm_pers_ws_bytes_slots": (i64, [i32, i32, i32]),
 }
 
 

@@ -2,19 +2,22 @@
 # Build the gfx950 library (cross-compiles without a GPU).  Each .hip is compiled to an object of its own, all in
 # parallel, and only when it (or a header) is newer than its object; then one link.
 #   csrc/build.sh [extra hipcc flags]        -> ../libdvae_hip.so   the product: one deterministic kernel dispatch
-#   csrc/build.sh dev [extra hipcc flags]    -> ../libdvae_dev.so   + probe kernels, environment tile knobs, in-kernel
-#                                                                     timelines (include/dvae_hip_dev.h; scripts/ only)
+#   csrc/build.sh dev [extra hipcc flags]    -> ../libdvae_dev.so   the same sources + dev_probes.hip, environment tile
+#                                                                     knobs, in-kernel timelines (include/dvae_hip_dev.h;
+#                                                                     scripts/ only)
 # FORCE=1 recompiles everything.
 set -euo pipefail
 HERE="$(cd "$(dirname "$0")" && pwd)"
 OUT="$HERE/../libdvae_hip.so"
 OBJ="$HERE/build/hip"
 DEFS=()
+SRCS=(gemm gemm256 lstm lstm_pers bn elem frontend prof repack probe val)
 if [ "${1:-}" = "dev" ]; then
   shift
   OUT="$HERE/../libdvae_dev.so"
   OBJ="$HERE/build/dev"
   DEFS=(-DDVAE_DEV -DDVAE_PERS_TS)
+  SRCS+=(dev_probes)
 fi
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -fvisibility=hidden -Wall -Wno-unused-function
@@ -30,7 +33,7 @@ HDR_NEWEST="$(ls -t "$HERE"/*.h "$HERE"/../../include/*.h | head -1)"
 pids=()
 objs=()
 compiled=()
-for f in gemm gemm256 lstm lstm_pers bn elem frontend prof repack probe val; do
+for f in "${SRCS[@]}"; do
   o="$OBJ/$f.o"
   objs+=("$o")
   if [ ! -f "$o" ] || [ "$HERE/$f.hip" -nt "$o" ] || [ "$HDR_NEWEST" -nt "$o" ]; then

@@ -26,11 +26,6 @@
 #include "common.h"
 #include "gemm_common.h"
 
-// Development ablations (build with -DDVAE_GEMM_ABL=<bits>, results are WRONG): 1 no operand split (one conversion),
-// 2 no global loads inside the k loop, 4 no LDS staging inside the loop, 8 no fragment reads inside the loop, 16 no MFMAs
-#ifndef DVAE_GEMM_ABL
-#define DVAE_GEMM_ABL 0
-#endif
 #ifndef DVAE_X3_PD
 #define DVAE_X3_PD 2   // k-tiles in flight ahead of the one being computed (split mode), see the kernel
 #endif
@@ -227,7 +222,6 @@ __global__ __launch_bounds__(64 * WG * WG) void gemm_f32_kernel(const GemmParams
         const int off = A_KC ? (idx / KQA) * LDA + 4 * (idx % KQA) : (idx / (BM / 4)) * LDA + 4 * (idx % (BM / 4));
         if constexpr (X3) {
           bf16x4 pl[3];
-          if constexpr (DVAE_GEMM_ABL & 1) pl[0] = pl[1] = pl[2] = __builtin_convertvector(ra[j], bf16x4); else
           split3(ra[j], pl);
 #pragma unroll
           for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(&As[buf][q * A_SZ + off]) = pl[q];
@@ -252,7 +246,6 @@ __global__ __launch_bounds__(64 * WG * WG) void gemm_f32_kernel(const GemmParams
         const int off = B_KC ? (idx / KQB) * LDB + 4 * (idx % KQB) : (idx / (BN / 4)) * LDB + 4 * (idx % (BN / 4));
         if constexpr (X3) {
           bf16x4 pl[3];
-          if constexpr (DVAE_GEMM_ABL & 1) pl[0] = pl[1] = pl[2] = __builtin_convertvector(rb[j], bf16x4); else
           split3(rb[j], pl);
 #pragma unroll
           for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x4*>(&Bs[buf][q * B_SZ + off]) = pl[q];
@@ -341,15 +334,9 @@ __global__ __launch_bounds__(64 * WG * WG) void gemm_f32_kernel(const GemmParams
 #pragma unroll
         for (int q = 0; q < NP; ++q) {
 #pragma unroll
-          for (int mt = 0; mt < 2; ++mt) {
-            if constexpr (DVAE_GEMM_ABL & 8) av[s2][mt][q] = __builtin_bit_cast(bf16x8, ra_[0][0]);
-            else av[s2][mt][q] = frag(&As[cur][q * A_SZ], A_KC, LDA, wm * 64 + mt * 32, s2);
-          }
+          for (int mt = 0; mt < 2; ++mt) av[s2][mt][q] = frag(&As[cur][q * A_SZ], A_KC, LDA, wm * 64 + mt * 32, s2);
 #pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) {
-            if constexpr (DVAE_GEMM_ABL & 8) bv[s2][nt][q] = __builtin_bit_cast(bf16x8, rb_[0][0]);
-            else bv[s2][nt][q] = frag(&Bs[cur][q * B_SZ], B_KC, LDB, wn * 32 * NTW + nt * 32, s2);
-          }
+          for (int nt = 0; nt < NTW; ++nt) bv[s2][nt][q] = frag(&Bs[cur][q * B_SZ], B_KC, LDB, wn * 32 * NTW + nt * 32, s2);
         }
       __builtin_amdgcn_sched_barrier(0);
       // X3: the six partial products of weight >= 2^-16, (a1,b1) first: it needs only the first image of each operand
@@ -361,12 +348,8 @@ __global__ __launch_bounds__(64 * WG * WG) void gemm_f32_kernel(const GemmParams
         for (int term = 0; term < NT6; ++term)
 #pragma unroll
           for (int nt = 0; nt < NTW; ++nt) {
-            if constexpr (DVAE_GEMM_ABL & 16) {
-              asm volatile("" ::"v"(av[s2][0][ia[term]]), "v"(av[s2][1][ia[term]]), "v"(bv[s2][nt][ib[term]]));
-            } else {
             acc[0][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[s2][0][ia[term]], bv[s2][nt][ib[term]], acc[0][nt], 0, 0, 0);
             acc[1][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[s2][1][ia[term]], bv[s2][nt][ib[term]], acc[1][nt], 0, 0, 0);
-            }
           }
       __builtin_amdgcn_sched_barrier(0);
     } else {
@@ -447,12 +430,12 @@ __global__ __launch_bounds__(64 * WG * WG) void gemm_f32_kernel(const GemmParams
 #pragma unroll
       for (int u = 0; u < PD; ++u) {
         // set u is free (tile it0+u was staged an iteration ago): tile it0 + u + PD goes there
-        if constexpr (!(DVAE_GEMM_ABL & 2)) load_tiles(ra_[u], rb_[u], tap_n, kit_n);
+        load_tiles(ra_[u], rb_[u], tap_n, kit_n);
         advance();
         compute_tile();
-        if constexpr (!(DVAE_GEMM_ABL & 4)) store_tiles(cur ^ 1, ra_[(u + 1) % PD], rb_[(u + 1) % PD]);
+        store_tiles(cur ^ 1, ra_[(u + 1) % PD], rb_[(u + 1) % PD]);
         __syncthreads();
-        if constexpr (!(DVAE_GEMM_ABL & 4)) cur ^= 1;
+        cur ^= 1;
       }
     }
   }
@@ -596,7 +579,7 @@ __global__ __launch_bounds__(64 * WG * WG) void gemm_f32_kernel(const GemmParams
 
 // ------------------------------------------------------------------------------------------------------------------
 // Split mode, 256 x 128 x 16 tile ("tall"): 4 waves (2 x 2), each a 128 x 64 output tile = 4 x 2 MFMA tiles, ONE
-// workgroup per CU, one wave per SIMD.  Why this shape (measured, scripts/coissue.py, gemm_ablate.py, mfma_peak.py):
+// workgroup per CU, one wave per SIMD.  Why this shape (measured, scripts/coissue.py, mfma_peak.py; DESIGN_HISTORY.md):
 //  * the split arithmetic of one wave and the MFMAs of ANOTHER wave of the same SIMD do not overlap at all (776 + 508
 //    cycles alone, 1284 together): two workgroups per CU (the 128 x 128 kernel) or two alternating wave groups buy no
 //    overlap for VALU-heavy staging — only instructions of the wave's OWN stream placed in the 32-cycle shadow of its

@@ -80,14 +80,6 @@ struct PersArgs {
   unsigned long long* ts;   // dev build: [frame][wave][8] s_memrealtime stamps of workgroup ts_bid (scripts/lstm_pers_timeline.py)
   int ts_bid;
 #endif
-#ifdef DVAE_DEV
-  // dev build, fp32x3 forward only (scripts/x3_fwd16_diag2.py): what every consumer had in its registers, frame by frame
-  unsigned* dbg;            // [frame][workgroup][thread][12]: xor-fold of the loaded fragments (4), pre-activations used (4), gate sums (4)
-  unsigned* dbg_frag;       // [frame][row group][wave][unit*3 + plane][lane][4]: the raw fragments of workgroups with jb == dbg_jb
-  int dbg_jb;
-  int nslot;                // ring slots (2; T = one per frame: no address is reused inside a launch)
-  int nodrain;              // TIMING EXPERIMENT ONLY (results may be wrong): the flag does not wait for the payload's acknowledgement
-#endif
 };
 
 #ifdef DVAE_PERS_TS
@@ -96,11 +88,7 @@ struct PersArgs {
 #define PERS_STAMP(p_) do {} while (0)
 #endif
 
-#ifdef DVAE_DEV
-#define PERS_DRAIN() do { if (!a.nodrain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } while (0)
-#else
 #define PERS_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#endif
 
 // ======================================================================================================================
 // XCD-LOCAL hand-off (round 6).  The write-through (sc1) stores of the flag protocol drop their lines from the XCD's L2, so every
@@ -910,9 +898,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void lstm_pers_fwd_x3(const PersArgs a
       }
     }
 
-#ifdef DVAE_DEV
-    if (a.dbg) *reinterpret_cast<f32x4*>(a.dbg + (((int64_t)step * gridDim.x + bid) * 256 + tid) * 12 + 4) = f32x4{x[0][0], x[0][1], x[0][2], x[0][3]};
-#endif
     PERS_STAMP(0);
     if (step > 0) {
       if (wave == NWV - 1 && !poll_ge(pflag, lane < NPR, epoch + (unsigned)step, a.timeout)) {
@@ -922,12 +907,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void lstm_pers_fwd_x3(const PersArgs a
       __syncthreads();                                             // barrier A
       PERS_STAMP(1);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#ifdef DVAE_DEV
-      const int so = ((step - 1) % a.nslot) * slot_bytes;
-      u32x4v dbg_ck = {0u, 0u, 0u, 0u};
-#else
       const int so = ((step - 1) & 1) * slot_bytes;
-#endif
       // unit u = (chunk k, row tile mt) = three 1-KiB fragments (the planes of h); RD units in flight
       bf16x8 av[RD][3];
       auto load = [&](int u) {
@@ -958,26 +938,12 @@ __global__ __launch_bounds__(64 * NWV, 1) void lstm_pers_fwd_x3(const PersArgs a
           acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[u % RD][0], w2[g], acc[mt][g], 0, 0, 0);
           acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[u % RD][2], W01[g][k][0], acc[mt][g], 0, 0, 0);
         }
-#ifdef DVAE_DEV
-        if (a.dbg) {
-#pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            const u32x4v raw = __builtin_bit_cast(u32x4v, av[u % RD][p]);
-            dbg_ck ^= raw;
-            if (a.dbg_frag && jb == a.dbg_jb)
-              *reinterpret_cast<u32x4v*>(a.dbg_frag + (((((int64_t)step * a.n_rb + rb) * NWV + wave) * (KW * MT * 3) + u * 3 + p) * 64 + lane) * 4) = raw;
-          }
-        }
-#endif
         if (u + RD < KW * MT) {
           __builtin_amdgcn_sched_barrier(0);
           load(u + RD);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-#ifdef DVAE_DEV
-      if (a.dbg) *reinterpret_cast<u32x4v*>(a.dbg + (((int64_t)step * gridDim.x + bid) * 256 + tid) * 12) = dbg_ck;
-#endif
     } else {
       fetch(min(step + 1, T - 1), x);
     }
@@ -1020,9 +986,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void lstm_pers_fwd_x3(const PersArgs a
         for (int sl = 0; sl < NWV - 1; ++sl) sacc += L.red[wave][sl][g][lane];
         if constexpr (MT == 2) { gs[g][0] = sacc[0]; gs[g][1] = sacc[1]; } else { gs[g][0] = sacc; }
       }
-#ifdef DVAE_DEV
-      if (a.dbg) *reinterpret_cast<f32x4*>(a.dbg + (((int64_t)step * gridDim.x + bid) * 256 + tid) * 12 + 8) = f32x4{gs[0][0], gs[1][0], gs[2][0], gs[3][0]};
-#endif
 #pragma unroll
       for (int i = 0; i < NEL; ++i) {
         const float gi = gate_sigmoid(gs[0][i]);
@@ -1050,11 +1013,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void lstm_pers_fwd_x3(const PersArgs a
     PERS_STAMP(5);
     if (wave == 0) {
       if ((step + 1 < T) && (bid != a.drop_bid)) {
-#ifdef DVAE_DEV
-        const int so = (step % a.nslot) * slot_bytes;
-#else
         const int so = (step & 1) * slot_bytes;
-#endif
         if (lane < 32) {                // lane (r, q' in {0,1}): units 8q'..8q'+7 of row r
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt)
@@ -1296,349 +1255,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void lstm_pers_fwd_x3h(const PersArgs 
   }
   pers_finish(a);
 }
-
-#ifdef DVAE_DEV
-// ======================================================================================================================
-// SENTINEL hand-off (round 5; DEV BUILD ONLY — measured slower than the flag protocol, kept as the reproducer of the 16-row
-// forward form's stale reads): the payload is its own flag.  Every ring word that is not yet this frame's data holds a
-// POISON no payload can contain (0xFFFFFFFF: two bf16 NaNs / an fp32 NaN with all mantissa bits set); a consumer loads
-// the fragments it needs straight into MFMA operand registers as before and looks at them: poison in any dword = not there
-// yet, load again.  No flag, no drain in front of it, no poll, no barrier between poll and loads — and a wave may ask for
-// the next frame's fragments BEFORE anybody has said they exist (speculative prefetch under the epilogue: for the slowest
-// workgroup of a row group, the one that sets the frame time, nearly everything is already there).
-//   ring   : FOUR slots; frame s lives in slot s & 3.
-//   publish: (wave 0, after barrier C of step s)  s_waitcnt vmcnt(0)  ->  data(s) into slot s & 3 (write-through, no drain)
-//            ->  poison into its own piece of slot (s+2) & 3.
-//   why that is enough: slot (s+2)&3 held frame s-2, whose last readers finished before they published frame s-1, and this
-//   workgroup has checked ALL of frame s-1 during step s: nobody reads those words any more.  A consumer asks for
-//   frame s+2 of this producer only after it has SEEN the producer's data(s+1), which was issued behind the vmcnt(0) that
-//   waited for the poison stores of step s: the poison is in memory before anybody can look for frame s+2 there, so a
-//   consumer sees poison or frame s+2, never frame s-2.  Slots 0 and 1 are poisoned by a small launch in front (every
-//   other slot by the producers themselves: step 0 poisons slot 2, step 1 slot 3, step 2 slot 0 ...).
-//   check  : every dword of every 16-byte piece (a torn 16-byte store would show as poison in some dword).
-//   waiting: the first lane that still sees poison re-reads ITS three pieces alone (one lane: no bandwidth) until they carry
-//            data, then the wave loads the unit again; bounded like every wait here.
-// The unit order of the wave that owns this workgroup's own chunk is rotated so that the own chunk comes LAST: it is never
-// part of the speculative prefetch (which runs before the workgroup has published).
-// ======================================================================================================================
-constexpr unsigned PERS_POISON = 0xFFFFFFFFu;
-constexpr int PERS_NSLOT_S = 4;
-
-__device__ __forceinline__ unsigned umax4(const u32x4v& v) {
-  const unsigned a = v[0] > v[1] ? v[0] : v[1], b = v[2] > v[3] ? v[2] : v[3];
-  return a > b ? a : b;
-}
-
-// wave-level: (re)load the NP pieces of one unit until none of them holds poison; `ld(p)` loads piece p for every active lane
-template <int NP, class LD>
-__device__ __forceinline__ bool sent_wait(u32x4v (&v)[NP], LD ld, int lane, unsigned timeout) {
-  auto poisoned = [&]() {
-    unsigned m = umax4(v[0]);
-#pragma unroll
-    for (int p = 1; p < NP; ++p) {
-      const unsigned x = umax4(v[p]);
-      m = x > m ? x : m;
-    }
-    return m == PERS_POISON;
-  };
-  bool bad = poisoned();
-  if (__builtin_expect(!__any(bad), 1)) return true;
-  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-  for (;;) {
-    const uint64_t mask = __ballot(bad);
-    if (!mask) return true;
-    const int first = __builtin_ctzll(mask);
-    bool gave_up = false;
-    if (lane == first) {
-      for (unsigned it = 1;; ++it) {
-        __builtin_amdgcn_s_sleep(2);
-#pragma unroll
-        for (int p = 0; p < NP; ++p) v[p] = ld(p);
-        if (!poisoned()) break;
-        if ((it & 15) == 0 && (__builtin_amdgcn_s_memrealtime() - t0) > timeout) { gave_up = true; break; }
-      }
-    }
-    if (__any(gave_up)) return false;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) v[p] = ld(p);
-    bad = poisoned();
-  }
-}
-
-template <int H, int K2L, int MT = 2>
-__global__ __launch_bounds__(64 * NWV, 1) void lstm_pers_fwd_x3s(const PersArgs a) {
-  constexpr int NCH = H / 32;           // 32-deep k-chunks of h
-  constexpr int KW = NCH / NWV;         // chunks per wave
-  constexpr int K2R = KW - K2L;         // chunks whose plane 2 stays in registers
-  constexpr int NEL = MT;
-  typedef typename x3_own<MT>::type own_t;
-  constexpr int NU = KW * MT;           // (chunk, row tile) units per wave and frame
-  constexpr int RD = PERS_RD_X3 < NU ? PERS_RD_X3 : NU;
-  constexpr int NPRE = RD < NU - MT ? RD : NU - MT;    // units asked for speculatively (never the last chunk: see above)
-  static_assert(NPRE >= 1, "speculative prefetch needs two chunks per wave");
-  const int T = a.T, N = a.N;
-  const int bid = blockIdx.x;
-  const int rb = bid % a.n_rb, jb = bid / a.n_rb;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 15, q = lane >> 4;
-
-  extern __shared__ __attribute__((aligned(16))) char lds_raw[];
-  X3Lds<KW, K2L, MT>& L = *reinterpret_cast<X3Lds<KW, K2L, MT>*>(lds_raw);
-  volatile int* dead = &L.dead;
-  if (tid == 0) *dead = 0;
-
-  // position kk of this wave's order is chunk wave*KW + (kk + koff) % KW: the workgroup's own chunk (jb >> 1) comes last
-  const int c_own = jb >> 1;
-  const int koff = (c_own / KW == wave) ? (c_own % KW + 1) % KW : 0;
-  auto chunk_of = [&](int kk) { return wave * KW + (kk + koff) % KW; };
-
-  bf16x8 W01[4][KW][2], W2[4][K2R > 0 ? K2R : 1];
-#pragma unroll
-  for (int g = 0; g < 4; ++g)
-#pragma unroll
-    for (int k = 0; k < KW; ++k)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        const bf16x8 w = *reinterpret_cast<const bf16x8*>(
-            a.wp + (((((int64_t)(g * (H / 16) + jb)) * NCH + chunk_of(k)) * 3 + p) * 64 + lane) * 16);
-        if (p < 2) W01[g][k][p < 2 ? p : 0] = w;
-        else if (k < K2R) W2[g][k < K2R ? k : 0] = w;
-        else L.w2[wave][g][k >= K2R ? k - K2R : 0][lane] = w;
-      }
-
-  const int emt = MT == 2 ? (wave >> 1) : 0, e0 = MT == 2 ? (wave & 1) * 2 : wave;
-  const int erow0 = emt * 16 + q * 4 + e0;
-  int el_n[NEL];
-  bool el_ok[NEL];
-  float creg[NEL];
-#pragma unroll
-  for (int i = 0; i < NEL; ++i) {
-    el_ok[i] = rb * 16 * MT + erow0 + i < N;
-    el_n[i] = min(rb * 16 * MT + erow0 + i, N - 1);
-    creg[i] = 0.f;
-  }
-  const int j0 = jb * 16;
-  const int64_t H4 = 4 * (int64_t)H;
-
-  const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.xch, 0, a.xch_bytes, 0x00020000);
-  const int slot_bytes = a.n_rb * NCH * MT * 3 * 1024;          // fragment (chunk, mt, plane) = 1 KiB
-  const int xrow = rb * NCH * MT * 3 * 1024 + lane * 16;        // + (chunk * MT + mt) * 3072 + plane * 1024
-  int xoff[KW];                                                 // per position kk: byte offset of its chunk inside a slot
-#pragma unroll
-  for (int k = 0; k < KW; ++k) xoff[k] = chunk_of(k) * MT * 3 * 1024;
-  const int xst = ((rb * NCH + (jb >> 1)) * MT * 3) * 1024 + ((jb & 1) * 32 + lane) * 16;
-
-  auto fetch = [&](int step_, float (&x)[NEL][4]) {
-    const int t_ = a.reverse ? (T - 1 - step_) : step_;
-    const float* __restrict__ G_ = a.gates + (int64_t)t_ * N * H4 + j0 + r;
-#pragma unroll
-    for (int i = 0; i < NEL; ++i)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) x[i][g] = G_[(int64_t)el_n[i] * H4 + g * H];
-  };
-
-  u32x4v av[RD][3];                     // units in flight: live ACROSS frames (the speculative prefetch)
-  // unit u = (position kk = u / MT, row tile mt = u % MT) of the frame in slot `so`
-  auto load = [&](int u, int so) __attribute__((always_inline)) {
-    const int kk = u / MT, mt = u % MT;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-      av[u % RD][p] = __builtin_amdgcn_raw_buffer_load_b128(xrs, xrow, so + xoff[kk] + (mt * 3 + p) * 1024, 16);   // ONE address register
-  };
-
-#ifdef DVAE_DEV
-  // dev build: nslot > 4 = one ring slot per frame, all poisoned in front of the launch, none re-poisoned here (no address
-  // is written twice in a launch: scripts/x3_fwd16_diag2.py)
-  const bool per_frame = a.nslot > PERS_NSLOT_S;
-  auto slot_of = [&](int s_) { return (per_frame ? s_ % a.nslot : (s_ & (PERS_NSLOT_S - 1))) * slot_bytes; };
-#else
-  constexpr bool per_frame = false;
-  auto slot_of = [&](int s_) { return (s_ & (PERS_NSLOT_S - 1)) * slot_bytes; };
-#endif
-  float x[NEL][4];
-  fetch(0, x);
-  __syncthreads();
-  for (int step = 0; step < T; ++step) {
-    const int t = a.reverse ? (T - 1 - step) : step;
-    f32x4 acc[MT][4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      f32x4 own = f32x4{0.f, 0.f, 0.f, 0.f};
-      if constexpr (MT == 2) {
-        if (e0) { own[2] = x[0][g]; own[3] = x[1][g]; } else { own[0] = x[0][g]; own[1] = x[1][g]; }
-        acc[0][g] = emt ? f32x4{0.f, 0.f, 0.f, 0.f} : own;
-        acc[1][g] = emt ? own : f32x4{0.f, 0.f, 0.f, 0.f};
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) own[e] = (e == e0) ? x[0][g] : 0.f;
-        acc[0][g] = own;
-      }
-    }
-
-    PERS_STAMP(0);
-    if (step > 0) {
-      const int so = slot_of(step - 1);
-      // units 0 .. NPRE-1 were asked for at the end of the previous step
-#pragma unroll
-      for (int u = NPRE; u < RD; ++u) load(u, so);
-      fetch(min(step + 1, T - 1), x);
-      __builtin_amdgcn_sched_barrier(0);
-      bf16x8 w2[4];
-      bool ok = true;
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        const int k = u / MT, mt = u % MT;
-        if (mt == 0) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-            w2[g] = (k < K2R) ? W2[g][k < K2R ? k : 0] : L.w2[wave][g][k >= K2R ? k - K2R : 0][lane];
-        }
-        ok = ok && sent_wait<3>(av[u % RD], [&](int p) __attribute__((always_inline)) {
-               return __builtin_amdgcn_raw_buffer_load_b128(xrs, xrow, so + xoff[k] + (mt * 3 + p) * 1024, 16); }, lane, a.timeout);
-#ifdef DVAE_DEV
-        if (a.dbg_frag && jb == a.dbg_jb) {
-#pragma unroll
-          for (int p = 0; p < 3; ++p)      // (in the wave's OWN unit order: position kk, not chunk)
-            *reinterpret_cast<u32x4v*>(a.dbg_frag + (((((int64_t)step * a.n_rb + rb) * NWV + wave) * (NU * 3) + u * 3 + p) * 64 + lane) * 4) = av[u % RD][p];
-        }
-#endif
-        const bf16x8 h0 = __builtin_bit_cast(bf16x8, av[u % RD][0]), h1 = __builtin_bit_cast(bf16x8, av[u % RD][1]),
-                     h2 = __builtin_bit_cast(bf16x8, av[u % RD][2]);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h0, W01[g][k][0], acc[mt][g], 0, 0, 0);
-          acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h0, W01[g][k][1], acc[mt][g], 0, 0, 0);
-          acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h1, W01[g][k][0], acc[mt][g], 0, 0, 0);
-          acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h1, W01[g][k][1], acc[mt][g], 0, 0, 0);
-          acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h0, w2[g], acc[mt][g], 0, 0, 0);
-          acc[mt][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h2, W01[g][k][0], acc[mt][g], 0, 0, 0);
-        }
-        if (u + RD < NU) {
-          __builtin_amdgcn_sched_barrier(0);
-          load(u + RD, so);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      if (!ok) {
-        pers_give_up(a.err, 1, bid, step, wave);
-        *dead = 1;
-      }
-    } else {
-      fetch(min(step + 1, T - 1), x);
-    }
-    // speculative prefetch of the next frame's first units (waves 1..3 here; wave 0 behind its publish below, which
-    // must not wait for these loads)
-    if (wave != 0 && step + 1 < T) {
-#pragma unroll
-      for (int u = 0; u < NPRE; ++u) load(u, slot_of(step));
-    }
-#pragma unroll
-    for (int o = 0; o < NWV; ++o) {
-      if (o == wave) continue;
-      const int slot = (wave - o - 1) & (NWV - 1);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if constexpr (MT == 2) {
-          const f32x4 v = acc[o >> 1][g];
-          L.red[o][slot][g][lane] = (o & 1) ? f32x2{v[2], v[3]} : f32x2{v[0], v[1]};
-        } else {
-          const f32x4 v = acc[0][g];
-          L.red[o][slot][g][lane] = o == 0 ? v[0] : o == 1 ? v[1] : o == 2 ? v[2] : v[3];
-        }
-      }
-    }
-    PERS_STAMP(2);
-    __syncthreads();                                               // barrier B
-    PERS_STAMP(3);
-    if (*dead) break;
-
-    float go_[NEL][4], co_[NEL], ho_[NEL];
-    {
-      float gs[4][NEL];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        own_t sacc;
-        if constexpr (MT == 2) {
-          f32x4 own = acc[0][g];
-          if (emt) own = acc[1][g];
-          sacc = e0 ? f32x2{own[2], own[3]} : f32x2{own[0], own[1]};
-        } else {
-          const f32x4 own = acc[0][g];
-          sacc = e0 == 0 ? own[0] : e0 == 1 ? own[1] : e0 == 2 ? own[2] : own[3];
-        }
-#pragma unroll
-        for (int sl = 0; sl < NWV - 1; ++sl) sacc += L.red[wave][sl][g][lane];
-        if constexpr (MT == 2) { gs[g][0] = sacc[0]; gs[g][1] = sacc[1]; } else { gs[g][0] = sacc; }
-      }
-#pragma unroll
-      for (int i = 0; i < NEL; ++i) {
-        const float gi = gate_sigmoid(gs[0][i]);
-        const float gf = gate_sigmoid(gs[1][i]);
-        const float gg = gate_tanh(gs[2][i]);
-        const float go = gate_sigmoid(gs[3][i]);
-        const float c = gf * creg[i] + gi * gg;
-        const float h = go * gate_tanh(c);
-        creg[i] = c;
-        const int row = erow0 + i;
-        const __bf16 h0 = (__bf16)h;
-        const float r1 = h - (float)h0;
-        const __bf16 h1 = (__bf16)r1;
-        const __bf16 h2 = (__bf16)(r1 - (float)h1);
-        L.hx[0][row >> 4][row & 15][r] = h0;
-        L.hx[1][row >> 4][row & 15][r] = h1;
-        L.hx[2][row >> 4][row & 15][r] = h2;
-        go_[i][0] = gi; go_[i][1] = gf; go_[i][2] = gg; go_[i][3] = go;
-        co_[i] = c; ho_[i] = h;
-      }
-    }
-    PERS_STAMP(4);
-    __syncthreads();                                               // barrier C
-    PERS_STAMP(5);
-    if (wave == 0 && step + 1 < T) {
-      if (bid != a.drop_bid) {
-        const int so = slot_of(step);
-        const int sp = slot_of(step + 2);
-        // the poison stores of the previous step (and everything older) have left: see the protocol above
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane < 32) {                // lane (r, q' in {0,1}): units 8q'..8q'+7 of row r
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-              const f32x4 v = *reinterpret_cast<const f32x4*>(&L.hx[p][mt][r][(q & 1) * 8]);
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, v), xrs, xst + (mt * 3 + p) * 1024, so, 16);
-            }
-          if (!per_frame) {
-            const u32x4v pz = {PERS_POISON, PERS_POISON, PERS_POISON, PERS_POISON};
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-              for (int p = 0; p < 3; ++p) __builtin_amdgcn_raw_buffer_store_b128(pz, xrs, xst + (mt * 3 + p) * 1024, sp, 16);
-          }
-        }
-        PERS_STAMP(6);
-      }
-#pragma unroll
-      for (int u = 0; u < NPRE; ++u) load(u, slot_of(step));
-    }
-    // the frame's outputs (activated gates, c, h)
-#pragma unroll
-    for (int i = 0; i < NEL; ++i) {
-      if (el_ok[i]) {
-        float* gp = a.gates + ((int64_t)t * N + el_n[i]) * H4 + j0 + r;
-        gp[0] = go_[i][0];
-        gp[H] = go_[i][1];
-        gp[2 * H] = go_[i][2];
-        gp[3 * H] = go_[i][3];
-        a.c_all[((int64_t)t * N + el_n[i]) * H + j0 + r] = co_[i];
-        reinterpret_cast<float*>(a.h_out)[((int64_t)t * N + el_n[i]) * a.ldh + j0 + r] = ho_[i];
-      }
-    }
-  }
-}
-
-#endif      // DVAE_DEV (sentinel hand-off)
 
 // ======================================================================================================================
 // fp32 backward (the default arithmetic keeps the backward recurrence on the fp32 MFMA: it streams the 4H-wide gate
@@ -2467,11 +2083,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void lstm_pers_bwd_x3k(const PersArgs 
 unsigned long long* g_pers_ts = nullptr;
 int g_pers_ts_bid = 0;
 #endif
-#ifdef DVAE_DEV
-unsigned* g_pers_dbg = nullptr;
-unsigned* g_pers_dbg_frag = nullptr;
-int g_pers_dbg_jb = 0, g_pers_nslot = 2;
-#endif
 int g_pers_cus = -1;
 int pers_cu_count() {
   if (g_pers_cus < 0) {
@@ -2495,18 +2106,6 @@ int pers_mt(int N, int H, int cus) {
 
 #ifndef PERS_KL
 #define PERS_KL 2
-#endif
-
-#ifdef DVAE_DEV
-// sentinel kernels: the first two ring slots are poisoned in front of the launch (write-through 16-byte stores; every other
-// slot by the producers themselves)
-__global__ __launch_bounds__(256) void pers_poison_kernel(char* __restrict__ xch, int bytes) {
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)xch, 0, bytes, 0x00020000);
-  const u32x4v pz = {PERS_POISON, PERS_POISON, PERS_POISON, PERS_POISON};
-  for (int o = (blockIdx.x * 256 + threadIdx.x) * 16; o < bytes; o += gridDim.x * 256 * 16)
-    __builtin_amdgcn_raw_buffer_store_b128(pz, rs, o, 0, 16);
-}
-
 #endif
 
 // one launch: LDS padded so that exactly one workgroup fits a CU
@@ -2533,18 +2132,9 @@ int pers_dispatch(int kind, int H, int mt, const PersArgs& a, int grid, hipStrea
       if (H == 1024) return pers_go(lstm_pers_bwd_bf16<1024, 2, KL>, (int)sizeof(BwdLds<2, KL>), a, grid, s);
       if (mt == 1) return pers_go(lstm_pers_bwd_bf16<512, 1, 0>, (int)sizeof(BwdLds<1, 0>), a, grid, s);
       return pers_go(lstm_pers_bwd_bf16<512, 2, 0>, (int)sizeof(BwdLds<2, 0>), a, grid, s);
-#ifdef DVAE_DEV
-    case 12:     // fp32x3 forward, sentinel hand-off
-      if (H == 1024) return pers_go(lstm_pers_fwd_x3s<1024, 8>, (int)sizeof(X3Lds<8, 8>), a, grid, s);
-      if (mt == 1) return pers_go(lstm_pers_fwd_x3s<512, 0, 1>, (int)sizeof(X3Lds<4, 0, 1>), a, grid, s);
-      return pers_go(lstm_pers_fwd_x3s<512, 0>, (int)sizeof(X3Lds<4, 0>), a, grid, s);
-#endif
     case 2:
       if (H == 1024) return pers_go(lstm_pers_fwd_x3<1024, 8>, (int)sizeof(X3Lds<8, 8>), a, grid, s);
-#ifdef DVAE_DEV      // (the 16-row forward form is not in the product library: see dvae_pers_launch)
-      if (mt == 1) return pers_go(lstm_pers_fwd_x3<512, 0, 1>, (int)sizeof(X3Lds<4, 0, 1>), a, grid, s);
-#endif
-      if (mt == 1) return DVAE_EINVAL;
+      if (mt == 1) return DVAE_EINVAL;      // (no 16-row forward form: DESIGN.md §4.2)
       return pers_go(lstm_pers_fwd_x3<512, 0>, (int)sizeof(X3Lds<4, 0>), a, grid, s);
     case 6:      // fp32x3 forward, 8 units x 32 rows (H = 512)
       return pers_go(lstm_pers_fwd_x3h<512>, (int)sizeof(X3HLds), a, grid, s);
@@ -2610,7 +2200,7 @@ DVAE_API int dvae_lstm_pers_supported(int N, int H, int mode, int bwd) {
   return dvae_pers_usable(N, H, mode, bwd);
 }
 
-static int64_t pers_ws_need(int T, int N, int H) {
+static int64_t pers_ws_need(int N, int H) {
   if (N < 1 || (H != 512 && H != 1024)) return 0;
   int64_t slot = 0;
   if (int mt = pers_mt(N, H, 256))
@@ -2618,9 +2208,9 @@ static int64_t pers_ws_need(int T, int N, int H) {
   if (pers_x3_ok(N, H, 256))
     for (int kind = 2; kind < 6; ++kind) slot = std::max(slot, pers_slot_bytes(kind, N, H, 2));
   if (!slot) return 0;
-  return PERS_XCH_OFF + (T > 0 ? (int64_t)T : 4) * slot;      // (two slots in use; four sized: the dev build's sentinel form)
+  return PERS_XCH_OFF + 4 * slot;      // (two slots in use; four sized: callers' workspaces are written against this value)
 }
-DVAE_API int64_t dvae_lstm_pers_ws_bytes(int N, int H) { return pers_ws_need(0, N, H); }
+DVAE_API int64_t dvae_lstm_pers_ws_bytes(int N, int H) { return pers_ws_need(N, H); }
 
 // one direction of one layer, all T frames; `bwd` selects the pass.  Returns DVAE_EINVAL when the shape has no persistent
 // kernel (the caller then uses the per-frame launches).
@@ -2642,29 +2232,17 @@ int dvae_pers_launch(const dvae_lstm_dir_t& d, bool bwd, int T, int N, int H, in
     if (d.packed_mode == DVAE_MODE_F32X3) kind = bwd ? (ks ? 5 : 4) : 2;
     else if (d.packed_mode == DVAE_MODE_F32 && bwd) kind = 3;
     else return DVAE_EINVAL;
-    // 16-row tiles where 32-row tiles would leave CUs idle (H = 512, N <= 128: 32 x 8 workgroups instead of 32 x 4);
-    // DVAE_PERS_X3_MT1=0 (dev build) keeps 32 rows
-    // bit 1: backward (measured 6.75 -> 4.66 us per frame; 0 failures in 300 rounds of scripts/x3_handoff_stress.py), bit 0:
-    // forward — DEV BUILD ONLY: 4.43 -> 3.41 us per frame, but 5-17 % of the stress rounds (a second stream streaming GiBs
-    // through HBM meanwhile) came back with rows 12..15 of one row group wrong in ALL columns from a frame around the 80th
-    // microsecond on.  Not the hand-off protocol (a release fence in front of the flag, an agent-scope acquire in front of
-    // the loads, sc0 sc1 loads, four ring slots, row groups spread over XCDs, a full vmcnt(0) after the loads: each still
-    // failed) and not found by reading the ISA; the 32-row forward kernel and every other persistent kernel: 0 of 200.
-    // scripts/x3_fwd16_diag.py: the stored h[t-1] of the bad rows is right and the bad gates match NO candidate input (h of
-    // another frame, another row, zeros) — in 3 of 4 cases they are off by more than any |h| < 1 could move them: the
-    // consumers' fragments held foreign bits in the 64-byte pieces of rows 12..15 (a fragment row group = lanes 12..15 of
-    // each 16-lane quarter), e.g. words an earlier launch left in the ring; once they were merely slightly off (1e-2).
+    // backward: 16-row tiles where 32-row tiles would leave CUs idle (H = 512, N <= 128: 32 x 8 workgroups instead of 32 x 4;
+    // measured 6.75 -> 4.66 us per frame; 0 failures in 300 rounds of scripts/x3_handoff_stress.py); DVAE_PERS_X3_MT1=0 (dev
+    // build, bit 1) keeps 32 rows.  The forward pass has no 16-row form: DESIGN.md §4.2.
     static const int mt1 = dvae_dev_knob("DVAE_PERS_X3_MT1", 2);
     const int n_rb16 = (N + 15) / 16;
-    if ((kind == 2 ? (mt1 & 1) : (mt1 & 2)) && (kind == 2 || kind == 4) && H == 512 &&
+    if ((mt1 & 2) && kind == 4 && H == 512 &&
         (H / 16) * ((N + 31) / 32) * 2 <= cus && n_rb16 <= 8 && (H / 16) * n_rb16 <= cus)
       mt = 1;
     // forward at H = 512: 8 units x 32 rows per workgroup (lstm_pers_fwd_x3h) where that fits the chip — 64 x 4 workgroups at
     // N = 128 instead of 32 x 4; DVAE_PERS_X3_H8=0 (dev build) keeps the 16-unit kernel
-    if (kind == 2 && mt == 2 && dvae_pers_fwd_units(N, H) == 8) units8 = true;
-#ifdef DVAE_DEV      // the diagnostics and the sentinel form exist for the 16-unit kernel only
-    if (g_pers_dbg || g_pers_nslot > 2 || dvae_dev_knob("DVAE_PERS_SENT", 0)) units8 = false;
-#endif
+    if (kind == 2 && dvae_pers_fwd_units(N, H) == 8) units8 = true;
   }
   PersArgs a{};
   a.gates = d.gates; a.wp = (const char*)d.w_packed; a.h_out = (char*)d.h_out; a.c_all = d.c_all;
@@ -2675,27 +2253,16 @@ int dvae_pers_launch(const dvae_lstm_dir_t& d, bool bwd, int T, int N, int H, in
   char* ws = (char*)d.pers_ws;
   a.flags = (unsigned*)ws; a.err = (unsigned*)(ws + PERS_ERR_OFF); a.xch = ws + PERS_XCH_OFF;
   a.T = T; a.N = N; a.ldh = ldh; a.reverse = d.reverse; a.s16 = d.state_bf16 ? 1 : 0;
-  a.n_rb = (N + 16 * mt - 1) / (16 * mt);      // (mt = 2 for every fp32x3 / fp32 kernel except the 16-row forms above)
+  a.n_rb = (N + 16 * mt - 1) / (16 * mt);      // (mt = 2 for every fp32x3 / fp32 kernel except the 16-row backward form above)
   const unsigned us = d.pers_timeout_us ? d.pers_timeout_us : 2000000u;
   a.timeout = us > 40000000u ? 4000000000u : us * 100u;
   const int64_t slot = pers_slot_bytes(kind, N, H, mt);
   a.xch_bytes = (int)(2 * slot);
-#ifdef DVAE_DEV
-  a.nslot = 2;
-  if (kind == 2) {      // diagnostics of the fp32x3 forward kernel (dvae_lstm_pers_set_dbg)
-    a.dbg = g_pers_dbg; a.dbg_frag = g_pers_dbg_frag; a.dbg_jb = g_pers_dbg_jb;
-    a.nslot = g_pers_nslot > 2 ? g_pers_nslot : 2;
-    a.xch_bytes = (int)(a.nslot * slot);     // (the caller sized the workspace: dvae_lstm_pers_ws_bytes_slots)
-  }
-#endif
   a.drop_bid = drop_bid;
   // XCD-local hand-off (pers_loc_*): the kernels that have it, where a row group's workgroups share bid % 8; the workgroups
   // verify their placement at frame 1.  DVAE_PERS_XCD_LOCAL=0 in the environment keeps every hand-off write-through.
   static const bool loc_env = []() { const char* e = getenv("DVAE_PERS_XCD_LOCAL"); return !(e && e[0] == '0'); }();
   a.local_ok = (loc_env && (kind == 0 || kind == 1 || (kind == 4 && !units8)) && (a.n_rb % 8) == 0) ? 1 : 0;
-#ifdef DVAE_DEV
-  a.nodrain = dvae_dev_knob("DVAE_PERS_NODRAIN", 0);
-#endif
 #ifdef DVAE_PERS_TS
   a.ts = g_pers_ts;
   a.ts_bid = g_pers_ts_bid;
@@ -2703,22 +2270,6 @@ int dvae_pers_launch(const dvae_lstm_dir_t& d, bool bwd, int T, int N, int H, in
   const int grid = (kind < 2 ? H / 32 : units8 ? H / 8 : H / 16) * a.n_rb;
   const size_t flag_bytes = kind == 5 ? (size_t)PERS_FLAG_BYTES      // + the partial flags behind the dG flags
                                       : (size_t)a.n_rb * (kind < 2 ? PERS_FLAG_LD : PERS_FLAG_LD_X3) * 4;
-#ifdef DVAE_DEV
-  static const int sent = dvae_dev_knob("DVAE_PERS_SENT", 0);      // dev build: 1 = the sentinel hand-off form of the fp32x3 forward kernel
-  if (kind == 2 && (sent & 1)) {
-    // sentinel hand-off: no flags; four slots, the first two poisoned here
-    // (the caller sized the workspace with dvae_lstm_pers_ws_bytes: four slots of the largest kind)
-    a.xch_bytes = (int)(PERS_NSLOT_S * slot);
-    int pb = (int)(2 * slot);
-    if (a.nslot > PERS_NSLOT_S) {      // one slot per frame (dvae_lstm_pers_set_dbg): all of them poisoned here
-      a.xch_bytes = (int)(a.nslot * slot);
-      pb = a.xch_bytes;
-    }
-    hipLaunchKernelGGL(pers_poison_kernel, dim3(std::min(1024, (pb / 16 + 255) / 256)), dim3(256), 0, s, a.xch, pb);
-    if (dvae_check_launch() != DVAE_OK) return DVAE_ELAUNCH;
-    return pers_dispatch(12, H, mt, a, grid, s);
-  }
-#endif
   // (no clearing launch: the flags carry the epoch of their launch, see pers_epoch)
   (void)flag_bytes;
   return pers_dispatch(units8 ? 6 : kind, H, mt, a, grid, s);
@@ -2752,18 +2303,6 @@ DVAE_API int dvae_lstm_pers_selftest(const dvae_lstm_dir_t* dir, int T, int N, i
   if (!dir) return DVAE_EINVAL;
   return dvae_pers_launch(*dir, false, T, N, H, ldh, drop_bid, (hipStream_t)stream);
 }
-
-#ifdef DVAE_DEV
-// dev build only (scripts/x3_fwd16_diag2.py): register dumps of the fp32x3 forward kernel, ring with `nslot` slots
-DVAE_API int dvae_lstm_pers_set_dbg(void* dbg, void* dbg_frag, int dbg_jb, int nslot) {
-  g_pers_dbg = (unsigned*)dbg;
-  g_pers_dbg_frag = (unsigned*)dbg_frag;
-  g_pers_dbg_jb = dbg_jb;
-  g_pers_nslot = nslot;
-  return DVAE_OK;
-}
-DVAE_API int64_t dvae_lstm_pers_ws_bytes_slots(int N, int H, int nslot) { return pers_ws_need(nslot, N, H); }
-#endif
 
 #ifdef DVAE_PERS_TS
 // dev build only (scripts/lstm_pers_timeline.py): stamps of workgroup `bid` go to buf[frame][wave][8]

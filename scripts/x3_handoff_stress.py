@@ -1,6 +1,7 @@
 """GPU box: the fp32x3 persistent recurrences (forward + backward) against the per-frame kernels under foreign HBM traffic,
 many rounds; prints which tensor / frame / row group went wrong when one does.
-usage: x3_handoff_stress.py H T N rounds      (DVAE_LIB_PATH + DVAE_PERS_X3_MT1 / DVAE_PERS_BWD_KSPLIT pick the kernels)"""
+usage: x3_handoff_stress.py H T N rounds      (DVAE_LIB_PATH = the dev library: DVAE_PERS_X3_MT1 picks the backward tiling,
+bit 1 = 16 rows at H = 512; DVAE_PERS_BWD_KSPLIT the k-split backward form; DVAE_PERS_X3_H8 the 8-unit forward form)"""
 import os
 import sys
 

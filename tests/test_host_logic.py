@@ -477,6 +477,52 @@ def test_ctypes_structs_follow_the_header():
     assert C.sizeof(_lib.SlabDesc) == 40
 
 
+def _dev_header_names():
+    import re
+    hdr = open(os.path.join(ROOT, "include", "dvae_hip_dev.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    return set(re.findall(r"\b(dvae_[a-z0-9_]+)\s*\(", hdr))
+
+
+def test_product_sources_carry_no_dev_code():
+    """The development build is the product's sources plus csrc/dev_probes.hip, the knobs of dvae_dev_knob (common.h) and the
+    timelines: no product translation unit has a DVAE_DEV branch, and the probe file is compiled for the dev library only."""
+    import re
+    csrc = os.path.join(ROOT, "disentangle-vae-for-vc_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f)))
+    assert "dev_probes.hip" in files and "lstm_pers.hip" in files
+    with_dev = [f for f in files if "DVAE_DEV" in open(os.path.join(csrc, f), errors="replace").read()]
+    assert with_dev == ["build.sh", "common.h"], with_dev
+    sh = open(os.path.join(csrc, "build.sh")).read()
+    product = re.findall(r"^SRCS=\(([^)]*)\)", sh, flags=re.M)
+    assert len(product) == 1, product
+    product = product[0].split()
+    assert len(product) == 11 and len(set(product)) == 11, product         # __graft_entry__.build() counts eleven objects
+    assert "dev_probes" not in product
+    assert all(f + ".hip" in files for f in product), product
+    dev_branch = sh[sh.index('= "dev" ]'):]
+    dev_branch = dev_branch[:dev_branch.index("\nfi\n")]
+    assert "SRCS+=(dev_probes)" in dev_branch
+    assert sh.count("dev_probes") == 2, "dev_probes: once in the header comment, once in the dev branch"
+    assert 'for f in "${SRCS[@]}"' in sh
+
+
+def test_dev_header_matches_dev_signatures():
+    from dvae_amd import _lib
+    names = _dev_header_names()
+    assert names == set(_lib.DEV_SIGNATURES), names ^ set(_lib.DEV_SIGNATURES)
+    assert len(names) >= 5 and not names & set(_lib.SIGNATURES)
+
+
+def test_product_library_exports_no_dev_entry_point():
+    import ctypes as C
+    from dvae_amd import _lib
+    h = C.CDLL(os.path.join(ROOT, "disentangle-vae-for-vc_amd", "libdvae_hip.so"))
+    assert hasattr(h, "dvae_version")
+    for n in sorted(_dev_header_names() | set(_lib.DEV_SIGNATURES)):
+        assert not hasattr(h, n), n
+
+
 def test_trajectory_band_is_monotone_and_floored(golden_dir):
     """conftest.trajectory_band: never below the 1e-4 of the single-step contract, non-decreasing over the steps inside each
     group of like losses, and the perturbed runs only widen it."""
