@@ -23,8 +23,8 @@ import math
 
 import numpy as np
 
-EPS32 = 2.0 ** -24
-FLOOR = 2.0 ** -126
+from ref_common import EPS32, FLOOR, worst_ratio  # noqa: F401
+
 # exact zeros, and magnitudes whose sqrt(v) is far below, near and far above eps = 1e-8
 GRAD_VALUES = np.array([0.0, 1e-30, -1e-30, 1e-12, -1e-12, 1e-8, -1e-8, 1e-4, -1e-4, 1.0, -1.0, 1e3, -1e3], dtype=np.float32)
 LR, BETAS, EPS = 1e-3, (0.9, 0.999), 1e-8
@@ -73,15 +73,6 @@ def one_step_bounds(p, g, m, v, lr, b1, b2, eps, gs, bc1, bc2s, cancel=False):
         tol_pc = EPS32 * np.abs(rp) + (8 * EPS32) * np.abs(u) + abs(float(lr) / float(bc1)) * tol_m / den + FLOOR
         out["tol_p_cancel"] = np.maximum(out["tol_p"], tol_pc)
     return out
-
-
-def worst_ratio(got, ref, tol):
-    """max |got - ref| / tol and where; 0 for empty input."""
-    if np.size(ref) == 0:
-        return 0.0, -1
-    r = np.abs(np.asarray(got, np.float64) - ref) / tol
-    i = int(np.argmax(r))
-    return float(r[i]), i
 
 
 def adam_step_f32(p, g, m, v, lr, b1, b2, eps, gs, bc1, bc2s):

@@ -64,25 +64,19 @@ dy (tol inside bwd_bounds)
     a sum of absolute values: cancellation inside the bracket is covered, FMA contraction only removes roundings.
 bf16 stores have no bound: they are the round-to-nearest-even of the fp32 value, compared bit for bit in the GPU tests.
 """
+import functools
+
 import numpy as np
 
-EPS32 = 2.0 ** -24
-EPS64 = 2.0 ** -53
-FLOOR = 2.0 ** -126
+import ref_common
+from ref_common import ACT_NONE, ACT_RELU, ACT_TANH, EPS32, EPS64, F, F64, FLOOR, fma as _fma, g  # noqa: F401
+
 ROWS_PER_CHUNK = 64                       # DVAE_BN_ROWS_PER_CHUNK of csrc/common.h
-ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 # Device tanhf against float64 tanh, |tanhf(x) - tanh(x)| / (eps32 |tanh(x)|): measured worst 2.4333 (at x = 0.634837687) over 40 000 001 evenly
 # spaced x in [-10, 10] and 2^23 log-spaced |x| in [1e-6, 10] on the MI355X (scripts/probes/tanhf_sweep.hip; DESIGN.md
 # section 5).  The sweep is a sample: the bound is twice that.
 TANHF_MEASURED = 2.4333
 TANHF_ROUNDINGS = 2.0 * TANHF_MEASURED
-
-F64 = np.float64
-
-
-def g(k):
-    """k fp32 roundings compounded."""
-    return k * EPS32 / (1.0 - k * EPS32)
 
 
 def groups(R, N, G):
@@ -269,19 +263,9 @@ def bwd_bounds(dz, y, z, mean, rstd, gamma, beta, N, G, act, old_dgamma=None, ol
     return out
 
 
-def worst_ratio(got, ref, tol):
-    """max |got - ref| / tol and where (a flat index); 0 for empty input.  Where the bound is +inf nothing is held (ratio 0);
-    anywhere else a value, a reference or a bound that is not finite counts as infinitely wrong."""
-    ref = np.asarray(ref, F64)
-    if ref.size == 0:
-        return 0.0, -1
-    got, tol = np.asarray(got, F64), np.broadcast_to(np.asarray(tol, F64), ref.shape)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        r = np.abs(got - ref) / tol
-    r = np.where(np.isposinf(tol), 0.0, r)
-    r = np.where(np.isfinite(got) & np.isfinite(ref) & ~np.isnan(tol) & ~np.isnan(r), r, np.inf)
-    i = int(np.argmax(r))
-    return float(r.reshape(-1)[i]), i
+# Where the bound is +inf nothing is held (ratio 0): the families that share this module's bounds (elem_ref, audio_ref) mark
+# the elements a kernel is not held at that way.
+worst_ratio = functools.partial(ref_common.worst_ratio, inf_tol_unheld=True)
 
 
 # ------------------------------------------------------------------ inputs of the tests (CPU and GPU alike)
@@ -342,14 +326,6 @@ def exact_zero_case():
 
 
 # ------------------------------------------------------------------ the kernels' statements in numpy float32
-F = np.float32
-
-
-def _fma(a, b, c):
-    """a * b + c with one rounding to fp32 (the product of two fp32 values is exact in float64)."""
-    return (np.asarray(a, F64) * np.asarray(b, F64) + np.asarray(c, F64)).astype(F)
-
-
 def _rows32(s, R, N, G):
     return np.asarray(s, F)[groups(R, N, G)]
 

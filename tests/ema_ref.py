@@ -32,9 +32,8 @@ import math
 
 import numpy as np
 
-EPS32 = 2.0 ** -24
-EPS64 = 2.0 ** -53
-FLOOR = 2.0 ** -126
+from ref_common import EPS32, EPS64, FLOOR, worst_ratio  # noqa: F401
+
 TICK_REL = 2.0 ** -23
 
 
@@ -70,15 +69,6 @@ def update_bounds(e, p, w):
     move = abs(w) * np.abs(p - e)
     tol = EPS32 * (move * (1.0 + EPS32) + np.abs(ref)) + 4.0 * EPS64 * (move + np.abs(e)) + FLOOR
     return {"ref": ref, "tol": tol}
-
-
-def worst_ratio(got, ref, tol):
-    """max |got - ref| / tol and where; 0 for empty input."""
-    if np.size(ref) == 0:
-        return 0.0, -1
-    r = np.abs(np.asarray(got, dtype=np.float64) - ref) / tol
-    i = int(np.argmax(r))
-    return float(r[i]), i
 
 
 def ema_update_f32(e, p, w, fused=True) -> np.ndarray:

@@ -82,36 +82,16 @@ import zlib
 
 import numpy as np
 
-EPS32 = 2.0 ** -24
-BF16_REL = 2.0 ** -8
-F, F64 = np.float32, np.float64
-MODE_F32, MODE_BF16, MODE_F32X3 = 0, 1, 2          # DVAE_MODE_* of include/dvae_hip.h
+from ref_common import (ACT_NONE, ACT_RELU, ACT_TANH, BF16_REL, EPS32, F, F64, MODE_BF16, MODE_F32, MODE_F32X3, bf16,  # noqa: F401
+                        bf16_trunc, split3)
+
 A_BF16, B_BF16, C_BF16 = 0x100, 0x200, 0x400
-ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 EPI_STORE, EPI_ACCUM, EPI_ATOMIC = 0, 1, 2
 MODES = {"fp32": MODE_F32, "bf16": MODE_BF16, "fp32x3": MODE_F32X3}
 TAPS = 5
 
 
 # ----------------------------------------------------------------------------------------------------------- arithmetic
-def bf16(x):
-    """Round-to-nearest-even bf16 of fp32 values, as fp32."""
-    u = np.ascontiguousarray(x, F).view(np.uint32)
-    return ((u + (((u >> 16) & 1) + 0x7FFF)) & 0xFFFF0000).astype(np.uint32).view(F)
-
-
-def bf16_trunc(x):
-    return (np.ascontiguousarray(x, F).view(np.uint32) & 0xFFFF0000).astype(np.uint32).view(F)
-
-
-def split3(x):
-    """x == x1 + x2 + x3 exactly, three bf16 planes: x1 = rne(x), x2 = rne(x - x1), x3 = x - x1 - x2 (gemm_common.h)."""
-    x = np.asarray(x, F)
-    x1 = bf16(x)
-    x2 = bf16(x - x1)
-    return x1, x2, bf16(x - x1 - x2)
-
-
 X3_TERMS = ((0, 0), (0, 1), (1, 0), (1, 1), (0, 2), (2, 0))      # a1b1 a1b2 a2b1 a2b2 a1b3 a3b1: weight >= 2^-16
 
 

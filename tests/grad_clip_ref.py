@@ -32,7 +32,8 @@ import math
 
 import numpy as np
 
-EPS32 = 2.0 ** -24
+from ref_common import EPS32  # noqa: F401
+
 NORM_REL = 2.0 ** -23
 EFF_REL = 4 * EPS32
 DENORM_FLOOR = 2.0 ** -149

@@ -74,11 +74,9 @@ import zlib
 
 import numpy as np
 
-EPS32 = 2.0 ** -24
-FLOOR = 2.0 ** -126
-BF16_REL = 2.0 ** -8
-F, F64 = np.float32, np.float64
-MODE_F32, MODE_BF16, MODE_F32X3 = 0, 1, 2          # DVAE_MODE_* of include/dvae_hip.h
+from ref_common import (BF16_REL, EPS32, F, F64, FLOOR, MODE_BF16, MODE_F32, MODE_F32X3, bf16, fma as _fma, g, split3,  # noqa: F401
+                        worst_ratio)
+
 # gate_sigmoid / gate_tanh of csrc/common.h against float64, worst |err| / 2^-24 over 40 000 001 evenly spaced x in
 # [-100, 100] and 2^23 log-spaced |x| in [1e-6, 100] of either sign on the MI355X (scripts/probes/gate_sweep.hip; DESIGN.md
 # section 5):  gate_sigmoid 1.8503 (at x = 3.60230398),  gate_tanh 3.6663 (at x = -1.78888464); nothing non-finite, every
@@ -89,25 +87,6 @@ GATE_TANH_MEASURED = 3.6663
 GATE_SIGMOID_ABS = 2.0 * GATE_SIGMOID_MEASURED
 GATE_TANH_ABS = 2.0 * GATE_TANH_MEASURED
 SATURATED = 90.0                 # |x| from which the probe found both gate functions exact
-
-
-def g(k):
-    """k fp32 roundings compounded."""
-    return k * EPS32 / (1.0 - k * EPS32)
-
-
-def bf16(x):
-    """Round-to-nearest-even bf16 of fp32 values, as fp32."""
-    u = np.ascontiguousarray(x, F).view(np.uint32)
-    return ((u + (((u >> 16) & 1) + 0x7FFF)) & 0xFFFF0000).astype(np.uint32).view(F)
-
-
-def split3(x):
-    """x == x1 + x2 + x3 exactly, three bf16 planes (fp32x3)."""
-    x = np.asarray(x, F)
-    x1 = bf16(x)
-    x2 = bf16(x - x1)
-    return x1, x2, bf16(x - x1 - x2)
 
 
 def operand(v, mode):
@@ -146,20 +125,6 @@ def rho(emul, ref, A):
     with np.errstate(divide="ignore", invalid="ignore"):
         r = np.where(A > 0, np.abs(np.asarray(emul, F64) - ref) / A, 0.0)
     return (float(r.max()), float(np.sqrt((r * r).mean()))) if r.size else (0.0, 0.0)
-
-
-def worst_ratio(got, ref, tol):
-    """max |got - ref| / tol and where (flat index).  A value, reference or bound that is not finite counts as infinitely
-    wrong."""
-    ref = np.asarray(ref, F64)
-    if ref.size == 0:
-        return 0.0, -1
-    got, tol = np.asarray(got, F64), np.broadcast_to(np.asarray(tol, F64), ref.shape)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        r = np.abs(got - ref) / tol
-    r = np.where(np.isfinite(got) & np.isfinite(ref) & np.isfinite(tol) & ~np.isnan(r), r, np.inf)
-    i = int(np.argmax(r))
-    return float(r.reshape(-1)[i]), i
 
 
 def _prod(factors, k):
@@ -478,10 +443,6 @@ def gate_sigmoid_f32(x):
 def gate_tanh_f32(x):
     with np.errstate(over="ignore", under="ignore"):
         return F(1) - F(2) * (F(1) / (np.exp(F(2) * np.asarray(x, F)) + F(1)))
-
-
-def _fma(a, b, c):
-    return (np.asarray(a, F64) * np.asarray(b, F64) + np.asarray(c, F64)).astype(F)
 
 
 def fwd_f32(x, W, h_prev, c_prev, mode, fma, product=None):

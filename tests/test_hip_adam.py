@@ -6,7 +6,7 @@ launch, `adam_step_ref` runs in float64 on those float32 values with the float32
 is compared with what the launch left.  No error accumulates, so the bounds are the rounding bounds derived in
 tests/adam_ref.py (eps32 = 2^-24, floor 2^-126):
     |m' - ref| <= 4 eps32 (|m| + |gs g|)      |v' - ref| <= 4 eps32 ref      |p' - ref| <= eps32 |ref| + 12 eps32 |u|
-Each buffer lies inside a larger allocation filled with a sentinel; the 64 floats on either side must keep their bits.
+Each buffer is a guarded one of tests/kernel_harness.py: the 256 bytes on either side must keep their bits.
 Inputs: p uniform in +-1, g drawn from {0, +-1e-30, +-1e-12, +-1e-8, +-1e-4, +-1, +-1e3} (sqrt(v) far below, near and far
 above eps), m = v = 0 before the first step and whatever the previous step left afterwards.
 
@@ -18,75 +18,43 @@ the two differ only for an element with |p| < 1e-3 whose first moment cancelled.
 12-rounding bound as stated has a test of its own (test_flat_adam_twenty_steps_p_meets_the_twelve_rounding_bound).
 """
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import bits, Buf, DEV, down, EINVAL, flat, guards, same_bits, st, sync, Worst      # first: it puts the repository root on sys.path
 import dvae_amd  # noqa: E402,F401
 from dvae_amd import _lib  # noqa: E402
 from dvae_amd._lib import Ranges  # noqa: E402
 from dvae_amd.optim import FlatAdam  # noqa: E402
 from adam_ref import BETAS, EPS, EPS32, LR, bias_corrections, grad_mixture, one_step_bounds, params, worst_ratio  # noqa: E402
 
-DEV = "cuda"
-PAD = 64                                   # sentinel floats on either side of every buffer
 SENT = np.float32(-7.5e11)                 # no step produces it
 B1F, B2F, EPSF, LRF = (np.float32(x) for x in (BETAS[0], BETAS[1], EPS, LR))
-EINVAL = -1
 BLOCK = 2048                               # elements per block and trip: 256 threads x 2 float4
 SIZES = [4, 1020, 1024, 1028, 2052, 4 * (2 * 1048576 + 256 + 3)]
-WORST = {"m": 0.0, "v": 0.0, "p": 0.0}     # over every raw-kernel and FlatAdam comparison of this module (printed at the end)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-def sync():
-    torch.cuda.synchronize()
-
-
-def stream():
-    return _lib.stream()
+WORST = Worst("test_hip_adam.py")          # over every raw-kernel and FlatAdam comparison of this module (printed at the end)
+WORST.worst.update(m=0.0, v=0.0, p=0.0)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def report():
     yield
-    print("\nworst error / bound over test_hip_adam.py: " + ", ".join(f"{k} {v:.3f}" for k, v in WORST.items()))
+    WORST.report()
 
 
-class Arena:
-    """p, g, m, v of n floats, each in the middle of an allocation of n + 2 PAD sentinels (16-byte aligned)."""
+def arena(n, seed):
+    """p, g, m, v of n floats, each in a guarded buffer of its own."""
+    return {k: Buf(data=a) for k, a in (("p", params(seed, n)), ("g", grad_mixture(seed + 1, n)), ("m", np.zeros(n, np.float32)),
+                                        ("v", np.zeros(n, np.float32)))}
 
-    def __init__(self, n, seed):
-        self.n = n
-        self.t = {k: torch.full((n + 2 * PAD,), float(SENT), dtype=torch.float32, device=DEV) for k in "pgmv"}
-        self.set("p", params(seed, n))
-        self.set("g", grad_mixture(seed + 1, n))
-        self.set("m", np.zeros(n, np.float32))
-        self.set("v", np.zeros(n, np.float32))
 
-    def set(self, k, a):
-        self.t[k][PAD:PAD + self.n].copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)))
-
-    def ptr(self, k, byte_offset=0):
-        return self.t[k].data_ptr() + 4 * PAD + byte_offset
-
-    def snap(self):
-        sync()
-        return {k: self.t[k].cpu().numpy().copy() for k in "pgmv"}
+def snap(ar):
+    """p, g, m, v as they are now; no launch so far wrote outside them."""
+    guards(*ar.values())
+    return {k: ar[k].np() for k in "pgmv"}
 
 
 def new_state(lr=LRF, gs=1.0):
@@ -104,10 +72,10 @@ def ranges(spans, n=None):
 
 
 def launch_dev(ar, state, n=None, skip=None, clear=None, tick=1, offsets=(0, 0, 0, 0)):
-    rc = _lib.lib().dvae_adam_flat_dev(*(ar.ptr(k, o) for k, o in zip("pgmv", offsets)), ar.n if n is None else n,
+    rc = _lib.lib().dvae_adam_flat_dev(*(ar[k].ptr + o for k, o in zip("pgmv", offsets)), ar["p"].shape[0] if n is None else n,
                                        float(B1F), float(B2F), float(EPSF), state.data_ptr(),
                                        None if skip is None else skip.data_ptr(),
-                                       None if clear is None else C.byref(clear), tick, stream())
+                                       None if clear is None else C.byref(clear), tick, st())
     sync()
     return rc
 
@@ -117,27 +85,24 @@ def unchanged(before, after, what=""):
         assert same_bits(before[k], after[k]), f"{what}: {k} changed"
 
 
-def check_step(before, after, n, sc, cleared=None, p_tol="tol_p", what=""):
-    """`after` is one step from `before` (whole allocations, sentinels included) with the scalars
+def check_step(before, after, sc, cleared=None, p_tol="tol_p", what=""):
+    """`after` is one step from `before` (`snap`, which has checked the guards, or whole flat buffers) with the scalars
     sc = (lr, b1, b2, eps, gs, bc1, bc2s); g is zero where `cleared` (a mask over [0, n)) and untouched elsewhere."""
-    inner = slice(PAD, PAD + n)
-    for k in "pgmv":
-        assert same_bits(before[k][:PAD], after[k][:PAD]), f"{what}: the 64 floats in front of {k} changed"
-        assert same_bits(before[k][PAD + n:], after[k][PAD + n:]), f"{what}: the 64 floats behind {k} changed"
-    g0, g1 = before["g"][inner], after["g"][inner]
+    n = len(before["p"])
+    g0, g1 = before["g"], after["g"]
     if cleared is None:
         cleared = np.zeros(n, dtype=bool)
     assert not bits(g1[cleared]).any(), f"{what}: a gradient inside a clear range is not +0.0"
     assert same_bits(g0[~cleared], g1[~cleared]), f"{what}: a gradient outside the clear ranges changed"
-    b = one_step_bounds(before["p"][inner], g0, before["m"][inner], before["v"][inner], *sc, cancel=(p_tol != "tol_p"))
+    b = one_step_bounds(before["p"], g0, before["m"], before["v"], *sc, cancel=(p_tol != "tol_p"))
     out = {}
     for k, tol in (("m", "tol_m"), ("v", "tol_v"), ("p", p_tol)):
-        r, i = worst_ratio(after[k][inner], b["ref_" + k], b[tol])
+        r, i = worst_ratio(after[k], b["ref_" + k], b[tol])
         out[k] = r
         if p_tol == "tol_p" or k != "p":
-            WORST[k] = max(WORST[k], r)
-        assert r <= 1.0, (f"{what}: {k}[{i}] = {after[k][inner][i]!r}, reference {b['ref_' + k][i]!r}, error / bound = {r:.3f} "
-                          f"(before: p {before['p'][inner][i]!r} g {g0[i]!r} m {before['m'][inner][i]!r} v {before['v'][inner][i]!r})")
+            WORST.record(k, r)
+        assert r <= 1.0, (f"{what}: {k}[{i}] = {after[k][i]!r}, reference {b['ref_' + k][i]!r}, error / bound = {r:.3f} "
+                          f"(before: p {before['p'][i]!r} g {g0[i]!r} m {before['m'][i]!r} v {before['v'][i]!r})")
     return out
 
 
@@ -159,58 +124,52 @@ def scalars(state_np):
     return (state_np[4], B1F, B2F, EPSF, state_np[5], state_np[1], state_np[2])
 
 
-def down(t):
-    sync()
-    return t.cpu().numpy().copy()
-
-
 # ------------------------------------------------------------------ dvae_adam_flat_dev through ctypes
 @pytest.mark.parametrize("n", SIZES)
 def test_dev_five_ticking_launches(n):
     """Sizes where only some threads have a second float4 (the clamped load, the guarded store), one block plus one float4,
     and two full grid-stride sweeps plus a ragged third."""
-    ar, state = Arena(n, seed=n % 1000), new_state()
+    ar, state = arena(n, seed=n % 1000), new_state()
     for t in range(1, 6):
-        before, s0 = ar.snap(), down(state)
+        before, s0 = snap(ar), down(state)
         assert launch_dev(ar, state) == 0
-        after, s1 = ar.snap(), down(state)
+        after, s1 = snap(ar), down(state)
         check_tick(s0, s1, t)
-        r = check_step(before, after, n, scalars(s1), what=f"n={n} t={t}")
+        r = check_step(before, after, scalars(s1), what=f"n={n} t={t}")
     print(f"n={n}: error / bound at t=5: " + ", ".join(f"{k} {v:.3f}" for k, v in r.items()))
 
 
 def test_dev_launch_without_tick_uses_the_corrections_that_are_there():
     n = 2052
-    ar, state = Arena(n, seed=7), new_state()
+    ar, state = arena(n, seed=7), new_state()
     for _ in range(2):
         assert launch_dev(ar, state) == 0
-    before, s0 = ar.snap(), down(state)
+    before, s0 = snap(ar), down(state)
     assert launch_dev(ar, state, tick=0) == 0
-    after, s1 = ar.snap(), down(state)
+    after, s1 = snap(ar), down(state)
     assert same_bits(s0, s1)
     assert s1[0] == 2.0
-    check_step(before, after, n, scalars(s0), what="tick=0")
+    check_step(before, after, scalars(s0), what="tick=0")
 
 
 @pytest.mark.parametrize("gs,lr", [(0.125, LRF), (3.0, LRF), (1.0, 0.0), (0.0, LRF)])
 def test_dev_grad_scale_and_learning_rate_come_from_dev_state(gs, lr):
     n = 2052
-    ar, state = Arena(n, seed=11), new_state()
+    ar, state = arena(n, seed=11), new_state()
     assert launch_dev(ar, state) == 0                       # moments that are not zero
     state[4:6].copy_(torch.tensor([float(lr), gs], dtype=torch.float32))
-    before, s0 = ar.snap(), down(state)
+    before, s0 = snap(ar), down(state)
     assert launch_dev(ar, state) == 0
-    after, s1 = ar.snap(), down(state)
+    after, s1 = snap(ar), down(state)
     check_tick(s0, s1, 2)
-    check_step(before, after, n, scalars(s1), what=f"gs={gs} lr={lr}")
-    inner = slice(PAD, PAD + n)
-    moved = before["g"][inner] != 0
+    check_step(before, after, scalars(s1), what=f"gs={gs} lr={lr}")
+    moved = before["g"] != 0
     assert moved.sum() > n // 2
     if lr == 0.0:
         assert same_bits(before["p"], after["p"])
-        assert (before["m"][inner][moved] != after["m"][inner][moved]).all()
-        squares = np.abs(before["g"][inner]) > 1e-15             # (1e-30)^2 is zero in fp32: v stays zero there
-        assert (before["v"][inner][squares] != after["v"][inner][squares]).all()
+        assert (before["m"][moved] != after["m"][moved]).all()
+        squares = np.abs(before["g"]) > 1e-15                    # (1e-30)^2 is zero in fp32: v stays zero there
+        assert (before["v"][squares] != after["v"][squares]).all()
     else:
         assert not same_bits(before["p"], after["p"])
 
@@ -226,50 +185,50 @@ def test_dev_clear_ranges(case):
     adjacent ones, one from the second float4, one up to n."""
     n = N_CLEAR
     spans = {"null": None, "none": [], "all": [(0, n)], "eight": EIGHT}[case]
-    ar, state = Arena(n, seed=13), new_state()
-    ar.set("g", np.where(grad_mixture(14, n) == 0, np.float32(1e-4), grad_mixture(14, n)))      # no zeros: a clear shows
+    ar, state = arena(n, seed=13), new_state()
+    ar["g"] = Buf(data=np.where(grad_mixture(14, n) == 0, np.float32(1e-4), grad_mixture(14, n)).astype(np.float32))      # no zeros
     mask = np.zeros(n, dtype=bool)
     for a, b in spans or []:
         mask[a:b] = True
     if case == "eight":
         assert all(a % BLOCK and b % BLOCK and a % 1024 and (b % 1024 or b == n) for a, b in EIGHT) and 0 < mask.sum() < n
-    before, s0 = ar.snap(), down(state)
+    before, s0 = snap(ar), down(state)
     assert launch_dev(ar, state, clear=None if spans is None else ranges(spans)) == 0
-    after, s1 = ar.snap(), down(state)
+    after, s1 = snap(ar), down(state)
     check_tick(s0, s1, 1)
-    check_step(before, after, n, scalars(s1), cleared=mask, what=case)
+    check_step(before, after, scalars(s1), cleared=mask, what=case)
     # the next step reads the cleared gradients: the moments decay there and follow the gradient elsewhere
     before, s0 = after, s1
     assert launch_dev(ar, state) == 0
-    after, s1 = ar.snap(), down(state)
-    check_step(before, after, n, scalars(s1), what=case + ", second step")
+    after, s1 = snap(ar), down(state)
+    check_step(before, after, scalars(s1), what=case + ", second step")
 
 
 @pytest.mark.parametrize("tick", [1, 0])
 def test_dev_skip_word_stops_everything(tick):
     n = 2052
-    ar, state = Arena(n, seed=17), new_state()
+    ar, state = arena(n, seed=17), new_state()
     assert launch_dev(ar, state) == 0
     word = torch.tensor([2, 0, 0, 0], dtype=torch.uint8, device=DEV)          # a uint32 holding 2
-    before, s0 = ar.snap(), down(state)
+    before, s0 = snap(ar), down(state)
     assert launch_dev(ar, state, skip=word, clear=ranges([(0, n)]), tick=tick) == 0
-    unchanged(before, ar.snap(), "skip word set")
+    unchanged(before, snap(ar), "skip word set")
     assert same_bits(s0, down(state))
     word.zero_()
     assert launch_dev(ar, state, skip=word, clear=ranges([(0, n)]), tick=tick) == 0
-    after, s1 = ar.snap(), down(state)
+    after, s1 = snap(ar), down(state)
     if tick:
         check_tick(s0, s1, 2)
     else:
         assert same_bits(s0, s1)
-    check_step(before, after, n, scalars(s1), cleared=np.ones(n, dtype=bool), what="skip word clear")
+    check_step(before, after, scalars(s1), cleared=np.ones(n, dtype=bool), what="skip word clear")
     assert not same_bits(before["p"], after["p"])
 
 
 def test_dev_refuses_bad_arguments_and_changes_nothing():
     n = 64
-    ar, state = Arena(n, seed=19), new_state()
-    before, s0 = ar.snap(), down(state)
+    ar, state = arena(n, seed=19), new_state()
+    before, s0 = snap(ar), down(state)
     calls = {
         "n = 0": dict(n=0), "n = 2": dict(n=2), "n = 6": dict(n=6),
         "misaligned p": dict(n=n - 4, offsets=(4, 0, 0, 0)), "misaligned g": dict(n=n - 4, offsets=(0, 8, 0, 0)),
@@ -284,10 +243,10 @@ def test_dev_refuses_bad_arguments_and_changes_nothing():
         assert launch_dev(ar, state, **kw) == EINVAL, what
     L = _lib.lib()
     for i in range(4):                                                                   # a null buffer, no state
-        ptrs = [None if j == i else ar.ptr(k) for j, k in enumerate("pgmv")]
-        assert L.dvae_adam_flat_dev(*ptrs, n, 0.9, 0.999, 1e-8, state.data_ptr(), None, None, 1, stream()) == EINVAL
-    assert L.dvae_adam_flat_dev(*(ar.ptr(k) for k in "pgmv"), n, 0.9, 0.999, 1e-8, None, None, None, 1, stream()) == EINVAL
-    unchanged(before, ar.snap(), "refused calls")
+        ptrs = [None if j == i else ar[k].ptr for j, k in enumerate("pgmv")]
+        assert L.dvae_adam_flat_dev(*ptrs, n, 0.9, 0.999, 1e-8, state.data_ptr(), None, None, 1, st()) == EINVAL
+    assert L.dvae_adam_flat_dev(*(ar[k].ptr for k in "pgmv"), n, 0.9, 0.999, 1e-8, None, None, None, 1, st()) == EINVAL
+    unchanged(before, snap(ar), "refused calls")
     assert same_bits(s0, down(state))
     assert launch_dev(ar, state, clear=ranges([(0, 4), (60, 64)])) == 0                  # ... and a good one is taken
     check_tick(s0, down(state), 1)
@@ -298,29 +257,29 @@ def test_dev_refuses_bad_arguments_and_changes_nothing():
 def test_host_scalar_entry_point(n):
     """float4 body plus the scalar tail of n % 4 elements; the large size is one full grid-stride sweep (4096 blocks), a
     ragged second one and a tail of three.  step = 1 from zero moments, then step = 7 on what that left; grad_scale 0.5."""
-    ar = Arena(n, seed=23 + n % 100)
+    ar = arena(n, seed=23 + n % 100)
     for step in (1, 7):
-        before = ar.snap()
-        rc = _lib.lib().dvae_adam_flat(*(ar.ptr(k) for k in "pgmv"), n, float(LRF), float(B1F), float(B2F), float(EPSF), 0.5,
-                                       step, stream())
+        before = snap(ar)
+        rc = _lib.lib().dvae_adam_flat(*(ar[k].ptr for k in "pgmv"), n, float(LRF), float(B1F), float(B2F), float(EPSF), 0.5,
+                                       step, st())
         assert rc == 0
-        after = ar.snap()
+        after = snap(ar)
         bc1, bc2s = (np.float32(x) for x in bias_corrections(float(B1F), float(B2F), step))      # as the entry point does
-        r = check_step(before, after, n, (LRF, B1F, B2F, EPSF, np.float32(0.5), bc1, bc2s), what=f"n={n} step={step}")
-        if (np.abs(before["g"][PAD:PAD + n]) >= 1e-8).any():
+        r = check_step(before, after, (LRF, B1F, B2F, EPSF, np.float32(0.5), bc1, bc2s), what=f"n={n} step={step}")
+        if (np.abs(before["g"]) >= 1e-8).any():
             assert not same_bits(before["p"], after["p"])
     print(f"n={n}: error / bound at step 7: " + ", ".join(f"{k} {v:.3f}" for k, v in r.items()))
 
 
 def test_host_scalar_entry_point_refuses():
-    ar = Arena(8, seed=29)
-    before = ar.snap()
-    L, ptrs = _lib.lib(), [ar.ptr(k) for k in "pgmv"]
-    assert L.dvae_adam_flat(*ptrs, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, 1, stream()) == EINVAL
-    assert L.dvae_adam_flat(*ptrs, 8, 1e-3, 0.9, 0.999, 1e-8, 1.0, 0, stream()) == EINVAL
-    assert L.dvae_adam_flat(ptrs[0] + 4, *ptrs[1:], 4, 1e-3, 0.9, 0.999, 1e-8, 1.0, 1, stream()) == EINVAL
-    assert L.dvae_adam_flat(None, *ptrs[1:], 8, 1e-3, 0.9, 0.999, 1e-8, 1.0, 1, stream()) == EINVAL
-    unchanged(before, ar.snap(), "refused calls")
+    ar = arena(8, seed=29)
+    before = snap(ar)
+    L, ptrs = _lib.lib(), [ar[k].ptr for k in "pgmv"]
+    assert L.dvae_adam_flat(*ptrs, 0, 1e-3, 0.9, 0.999, 1e-8, 1.0, 1, st()) == EINVAL
+    assert L.dvae_adam_flat(*ptrs, 8, 1e-3, 0.9, 0.999, 1e-8, 1.0, 0, st()) == EINVAL
+    assert L.dvae_adam_flat(ptrs[0] + 4, *ptrs[1:], 4, 1e-3, 0.9, 0.999, 1e-8, 1.0, 1, st()) == EINVAL
+    assert L.dvae_adam_flat(None, *ptrs[1:], 8, 1e-3, 0.9, 0.999, 1e-8, 1.0, 1, st()) == EINVAL
+    unchanged(before, snap(ar), "refused calls")
 
 
 # ------------------------------------------------------------------ FlatAdam on the device
@@ -361,12 +320,6 @@ def feed(opt, seed):
     return out
 
 
-def flat(opt):
-    sync()
-    return {"p": opt.flat_p.cpu().numpy().copy(), "g": opt.flat_g.cpu().numpy().copy(), "m": opt.exp_avg.cpu().numpy().copy(),
-            "v": opt.exp_avg_sq.cpu().numpy().copy()}
-
-
 def padding(opt):
     pad = np.ones(opt.numel, dtype=bool)
     for n, p in zip(opt.names, opt.params):
@@ -380,12 +333,6 @@ def zero_mask(opt, lo=0, hi=None):
         for a, b in opt._zero_ranges:
             mask[max(a, lo):min(b, opt.numel if hi is None else hi)] = True
     return mask
-
-
-def check_flat_step(before, after, sc, cleared, what, p_tol="tol_p"):
-    """check_step over whole flat buffers (no sentinels around them: torch owns the allocations)."""
-    wrap = lambda d: {k: np.concatenate([np.zeros(PAD, np.float32), x, np.zeros(PAD, np.float32)]) for k, x in d.items()}
-    return check_step(wrap(before), wrap(after), len(before["p"]), sc, cleared=cleared, p_tol=p_tol, what=what)
 
 
 @pytest.fixture(scope="module")
@@ -408,10 +355,10 @@ def twenty_steps():
         res["t"].append((float(s1[0]), opt.t))
         res["pad_nonzero"] += sum(int(bits(after[k][pad]).any()) for k in "pgmv")
         # every check of one step but the 12-rounding bound of p, which gets a test of its own (module docstring)
-        res["ratios"].append(check_flat_step(before, after, scalars(s1), zero_mask(opt), f"step {t}", p_tol="tol_p_cancel"))
+        res["ratios"].append(check_step(before, after, scalars(s1), zero_mask(opt), "tol_p_cancel", f"step {t}"))
         b = one_step_bounds(before["p"], before["g"], before["m"], before["v"], *scalars(s1))
         res["p_literal"].append(worst_ratio(after["p"], b["ref_p"], b["tol_p"])[0])
-        WORST["p"] = max(WORST["p"], res["p_literal"][-1])
+        WORST.record("p", res["p_literal"][-1])
     res["p"] = np.concatenate([down(p.detach()).reshape(-1) for p in opt.params]).astype(np.float64)
     res["p_torch"] = np.concatenate([r.detach().numpy().reshape(-1) for r in ref])
     return res
@@ -499,7 +446,7 @@ def test_one_step_range_touches_only_its_piece(variant):
     cut = lambda d: {k: x[lo:hi] for k, x in d.items()}
     cleared = zero_mask(opt, lo, hi)[lo:hi]
     assert cleared.sum() == {"fold": hi - lo, "store_first": hi - 1192, "no_fold": 0}[variant]
-    check_flat_step(cut(before), cut(after), scalars(s1), cleared, f"{variant} [{lo}, {hi})")
+    check_step(cut(before), cut(after), scalars(s1), cleared, what=f"{variant} [{lo}, {hi})")
     assert not same_bits(before["p"][lo:hi], after["p"][lo:hi])
 
 
@@ -538,7 +485,7 @@ def test_zero_grad_scale_is_honoured_and_none_keeps_the_last():
         opt.step(grad_scale=gs)
         after, s1 = flat(opt), down(opt.dev_state)
         assert s1[0] == float(t) and s1[5] == 0.0
-        check_flat_step(before, after, scalars(s1), zero_mask(opt), f"grad_scale={gs}")
+        check_step(before, after, scalars(s1), zero_mask(opt), what=f"grad_scale={gs}")
         live = before["m"] != 0
         assert live.sum() > opt.numel // 2
         assert np.abs(after["m"][live]).max() < np.abs(before["m"][live]).max()

@@ -4,67 +4,30 @@ reference of tests/audio_ref.py, element by element.
 What audio_ref derives as bit-exact is compared bit for bit (the frames, every class-E case, the zero phase, the |a| = 0
 branch, the clips, the floor, zero fills, copies, the volume partials), everything else within the rounding bounds derived
 there from eps32 = 2^-24, the operation counts and the measured device-function constants, at 100 % of the elements.  Every
-buffer a launch may write lies between 256 guard bytes and is 0xFF before the launch (an unwritten fp32 is a NaN and keeps
-the bits 0xFFFFFFFF); every region an entry point must not read holds NaN (`Pad`: NaN in front of and behind every input,
-in the gaps of every leading dimension).  The worst error / bound per kernel and quantity is printed at the module's end.
+buffer a launch may write is a guarded one of tests/kernel_harness.py (an unwritten fp32 keeps the bits 0xFFFFFFFF); every
+region an entry point must not read holds NaN (`Pad`: NaN in front of and behind every input, in the gaps of every leading
+dimension).  The worst error / bound per kernel and quantity is printed at the module's end.
 """
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import assert_same_bits, Buf, EINVAL, F32, F64, guards, ibuf, L, ok, Pad, st, untouched, Worst
 import dvae_amd  # noqa: E402,F401
-from dvae_amd import _lib  # noqa: E402
 import audio_ref as A  # noqa: E402
-import test_hip_elem as H  # noqa: E402
-from test_hip_elem import Buf, guards, same_bits, ok, L, st  # noqa: E402
 from test_audio_ref import (PARAMS, dtw_r_case, gl_phase_case, log_power_case, ola_case, voicing_r_case)  # noqa: E402
 
-F32, F64 = np.float32, np.float64
-EINVAL = -1
-WORST = {}
+WORST = Worst("test_hip_audio.py", sort=True, ratio_fn=A.worst_ratio)
+note = WORST.note
 I64 = torch.int64
-
-
-def note(key, got, ref, tol, what):
-    """test_hip_elem.note, its entry kept in this module's table"""
-    try:
-        H.note("audio " + key, got, ref, tol, what)
-    finally:
-        if "audio " + key in H.WORST:
-            WORST[key] = max(WORST.get(key, 0.0), H.WORST.pop("audio " + key))
 
 
 @pytest.fixture(scope="module", autouse=True)
 def report():
     yield
-    print("\nworst error / bound over test_hip_audio.py: " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(WORST.items())))
-
-
-class Pad:
-    """An input of the launch: `data` (fp32) with `before` and `after` NaN elements around it in one guarded buffer;
-    .ptr is the address of data[0]."""
-
-    def __init__(self, data, before=4, after=64):
-        data = np.ascontiguousarray(data, F32)
-        flat = np.concatenate([np.full(before, np.nan, F32), data.reshape(-1), np.full(after, np.nan, F32)])
-        self.buf = Buf(None, data=flat)
-        self.ptr = self.buf.ptr + 4 * before
-
-
-def ibuf(a, dtype=np.int64):
-    a = np.ascontiguousarray(a, dtype)
-    return Buf(None, dtype={np.int64: I64, np.int32: torch.int32}[dtype], data=a)
-
-
-def untouched(bits_, what):
-    assert (np.asarray(bits_).reshape(-1) == -1).all(), f"{what}: an element the launch must not write changed"
+    WORST.report()
 
 
 # ------------------------------------------------------------------ stft_frames
@@ -78,7 +41,7 @@ def test_stft_frames(fsize, hop, left, n, integer):
     bw, bwin, out = Pad(wav), Pad(win), Buf((M, fsize))
     ok(L().dvae_stft_frames(bw.ptr, n, bwin.ptr, out.ptr, M, fsize, hop, left, st()))
     guards(out)
-    same_bits(out, A.frames_ref(wav, win, A.seg_table([M], [n]), M, fsize, hop, left), f"stft_frames {fsize}/{hop} left={left} n={n}")
+    assert_same_bits(out, A.frames_ref(wav, win, A.seg_table([M], [n]), M, fsize, hop, left), f"stft_frames {fsize}/{hop} left={left} n={n}")
 
 
 @pytest.mark.parametrize("fsize,hop,left,ns", A.CASES["frames_seg"])
@@ -90,7 +53,7 @@ def test_stft_frames_seg(fsize, hop, left, ns):
     bw, bwin, bs, out = Pad(wav), Pad(win), ibuf(seg), Buf((rows, fsize))
     ok(L().dvae_stft_frames_seg(bw.ptr, bs.ptr, len(ns), rows, bwin.ptr, out.ptr, fsize, hop, left, st()))
     guards(out)
-    same_bits(out, A.frames_ref(wav, win, seg, rows, fsize, hop, left), f"stft_frames_seg {fsize}/{hop}")
+    assert_same_bits(out, A.frames_ref(wav, win, seg, rows, fsize, hop, left), f"stft_frames_seg {fsize}/{hop}")
 
 
 # ------------------------------------------------------------------ magnitude, gl_init, gl_phase
@@ -109,7 +72,7 @@ def test_stft_magnitude(rows, nbp):
     be, oe = Pad(e), Buf((rows, nbp))
     ok(L().dvae_stft_magnitude(be.ptr, oe.ptr, rows, nbp, st()))
     guards(oe)
-    same_bits(oe, 5 * sc, "stft_magnitude class E")
+    assert_same_bits(oe, 5 * sc, "stft_magnitude class E")
 
 
 @pytest.mark.parametrize("rows,nbp", A.CASES["rows_nbp"])
@@ -121,7 +84,7 @@ def test_gl_init(rows, nbp):
     out = Buf((rows, 2 * nbp))
     ok(L().dvae_gl_init(bm.ptr, None, out.ptr, rows, nbp, st()))
     guards(out)
-    same_bits(out, np.concatenate([mag, np.zeros_like(mag)], 1), "gl_init without a phase")
+    assert_same_bits(out, np.concatenate([mag, np.zeros_like(mag)], 1), "gl_init without a phase")
     out = Buf((rows, 2 * nbp))
     ok(L().dvae_gl_init(bm.ptr, bp.ptr, out.ptr, rows, nbp, st()))
     guards(out)
@@ -141,7 +104,7 @@ def test_gl_phase(rows, nbp):
         ref, tol, zero = A.gl_phase_bounds(reb, pv, mag, nbp, mom)
         got = out.np()
         note("gl_phase", got, ref, tol, f"rows={rows} nbp={nbp} prev={pv is not None} momentum={mom}")
-        same_bits(got[zero], ref[zero].astype(F32), "gl_phase where |a| = 0: (mag, +0)")
+        assert_same_bits(got[zero], ref[zero].astype(F32), "gl_phase where |a| = 0: (mag, +0)")
         if pv is not None and mom > 0:
             assert zero.any()
 
@@ -231,26 +194,26 @@ def test_mel_nnls_pg(nbp, C, rows):
     x0, amp = rs.randint(0, 5, (rows, nbp)).astype(F32), rs.randint(0, 9, (rows, C)).astype(F32)
     rc, bx = nnls_launch(amp, x0, fr, bf, bw, 2.0 ** -3, 3)
     ok(rc)
-    same_bits(bx, A.nnls_bounds(x0, amp, fr, bf, bw, 2.0 ** -3, 3)[0].astype(F32), f"nnls class E nbp={nbp} C={C}")
+    assert_same_bits(bx, A.nnls_bounds(x0, amp, fr, bf, bw, 2.0 ** -3, 3)[0].astype(F32), f"nnls class E nbp={nbp} C={C}")
     fr, bf, bw, dense = A.mel_tables(nbp, C, rs, integer=False)
     x0, amp = np.abs(A.rfull(rs, (rows, nbp), -4, 2)), np.abs(A.rfull(rs, (rows, C), -4, 2))
     step = F32(0.9 / np.linalg.norm(dense, 2) ** 2)
     rc, bx = nnls_launch(amp, x0, fr, bf, bw, step, 0)
     ok(rc)
-    same_bits(bx, x0, "nnls iters = 0 leaves x alone")
+    assert_same_bits(bx, x0, "nnls iters = 0 leaves x alone")
     rc, bx = nnls_launch(amp, x0, fr, bf, bw, step, 1)
     ok(rc)
     ref, tol, _ = A.nnls_bounds(x0, amp, fr, bf, bw, step, 1)
     got = bx.np()
     note("mel_nnls_pg one step", got, ref, tol, f"nbp={nbp} C={C}")
     unf = ~dense.any(0)
-    same_bits(got[:, unf], x0[:, unf], "a bin under no filter keeps its bits")
+    assert_same_bits(got[:, unf], x0[:, unf], "a bin under no filter keeps its bits")
     rc, bx = nnls_launch(amp, x0, fr, bf, bw, step, 7)
     ok(rc)
     ref, _, n2 = A.nnls_bounds(x0, amp, fr, bf, bw, step, 7)
     err = np.sqrt(((bx.np().astype(F64) - ref) ** 2).sum(1))
     note("mel_nnls_pg 7 steps, row 2-norm", err, np.zeros(rows), n2, f"nbp={nbp} C={C}")
-    same_bits(bx.np()[:, unf], x0[:, unf], "a bin under no filter keeps its bits")
+    assert_same_bits(bx.np()[:, unf], x0[:, unf], "a bin under no filter keeps its bits")
 
 
 def test_mel_nnls_pg_refusals():
@@ -296,7 +259,7 @@ def test_ola_gather(fsize, hop, integer):
                 ref, tol = A.ola_bounds(y, win, segs, rows, out_len, fsize, hop, mode, norm)
                 what = f"ola {fsize}/{hop} mode={mode} norm={norm} gap={gap}"
                 if integer:
-                    same_bits(out, ref.astype(F32), what + " class E")
+                    assert_same_bits(out, ref.astype(F32), what + " class E")
                 else:
                     note(f"ola_gather mode {mode}" + (" norm" if norm else ""), out.np(), ref, tol, what)
                     assert not out.bits()[ref == 0].any() or mode == 0, what + ": a gap is not +0"
@@ -355,7 +318,7 @@ def resample_run(filters, weights, table, tiles, x, what, integer):
     assert np.isfinite(got[written]).all(), what + ": the NaN sentinel (or an unwritten output) inside a segment"
     untouched(gb[~written], what + " between the segments")
     if integer:
-        same_bits(got[written], ref[written].astype(F32), what + " class E")
+        assert_same_bits(got[written], ref[written].astype(F32), what + " class E")
     else:
         note("resample_batch", got[written], ref[written], tol[written], what)
     for in0, n, out0, n_out, nv, f in table:
@@ -430,7 +393,7 @@ def test_volume_normalize(increase_only):
     gd, got = gain.np(), by.np()
     assert gd[1] == 1.0 and (gd[2] == 1.0) == bool(increase_only) and (gd[7] == 1.0) == bool(increase_only)
     for s, (_, n, out0, *_r) in enumerate(segs):
-        same_bits(got[out0:out0 + n], y[out0:out0 + n] * F32(gd[s]), f"volume segment {s}: y * the device's own gain")
+        assert_same_bits(got[out0:out0 + n], y[out0:out0 + n] * F32(gd[s]), f"volume segment {s}: y * the device's own gain")
     assert np.isnan(got[np.isnan(y)]).all()
     assert L().dvae_volume_normalize(by.ptr, bs.ptr, len(n_outs), bt.ptr, len(tiles), bf.ptr, part.ptr, 2000.0, 0, ms.ptr, gain.ptr,
                                      silent.ptr, st()) == EINVAL
@@ -458,7 +421,7 @@ def test_log_power(rows, nb, nbp):
     guards(pe, le)
     want = 2 * sc * sc
     want[:, nb:] = 0
-    same_bits(pe, want, "log_power class E")
+    assert_same_bits(pe, want, "log_power class E")
     assert L().dvae_log_power(be.ptr, pe.ptr, le.ptr, rows, nbp + 1, nbp, floor, st()) == EINVAL
 
 
@@ -474,11 +437,11 @@ def voicing_launch(r, ldr, nlag, gain, mc, ldm, segs, peak_min, rel_min):
 
 
 def check_voicing_exact(b, peak, voiced, feats, count, what):
-    same_bits(peak, b["peak"].astype(F32), what + " peak")
+    assert_same_bits(peak, b["peak"].astype(F32), what + " peak")
     assert np.array_equal(voiced.np(), b["voiced"]), what + " voiced"
     assert np.array_equal(count.np(), b["count"]), what + " count"
     fb, wr = feats.bits(), ~np.isnan(b["feats"][:, 0])
-    same_bits(feats.np()[wr], b["feats"][wr], what + " feats")
+    assert_same_bits(feats.np()[wr], b["feats"][wr], what + " feats")
     untouched(fb[~wr], what + " feats beyond row0 + count")
 
 
@@ -520,7 +483,7 @@ def test_voicing_compact_class_r(M):
         v = voiced.np()
         assert np.array_equal(v[dec], b["voiced"][dec]), f"voicing R M={M} nlag={nlag}: a decided flag differs"
         assert count.np()[0] == v.sum()
-        same_bits(feats.np()[:v.sum()], mc[v.astype(bool), :24], "feats: the voiced rows in time order")
+        assert_same_bits(feats.np()[:v.sum()], mc[v.astype(bool), :24], "feats: the voiced rows in time order")
         untouched(feats.bits()[v.sum():], "feats beyond count")
 
 

@@ -7,101 +7,32 @@ what the launch left.  The bounds are the rounding bounds derived in tests/bn_re
 channel, never a fraction of a tensor's maximum.  bf16 stores have no bound: they must be bit-equal to the
 round-to-nearest-even bf16 of the fp32 output of the same launch made with fp32 storage.
 
-Every buffer a launch may write lies inside a larger allocation with 64 floats (256 bytes) of a guard pattern on either
-side, the workspace inside one of dvae_bn_ws_bytes with the same guards, filled with 0xFF before each launch (an unwritten
-partial is a NaN); the guards must keep their bits.  bn.hip does not read the compute mode, so nothing is parametrised
-over it.  The worst error / bound per quantity over the module is printed at its end.
+Every buffer a launch may write, the workspace of dvae_bn_ws_bytes included, is a guarded one of tests/kernel_harness.py.
+bn.hip does not read the compute mode, so nothing is parametrised over it.  The worst error / bound per quantity over the
+module is printed at its end.
 """
 import functools
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import dvae_amd  # noqa: E402,F401
-from dvae_amd import _lib  # noqa: E402
+from kernel_harness import Buf, EINVAL, guards, L, P, st, sync, Worst      # first: it puts the repository root on sys.path
 import bn_ref as B  # noqa: E402
 
-DEV = "cuda"
-PADB = 256                                  # guard bytes on either side of every buffer: 64 floats
-GUARD = 0xA5
-EINVAL = -1
 EPSF, MOMF = np.float32(1e-5), np.float32(0.1)
 ACTS = {"none": B.ACT_NONE, "relu": B.ACT_RELU, "tanh": B.ACT_TANH}
 CASE_IDS = ["x".join(map(str, c)) for c in B.CASES]
 BIG = B.CASES[-1]
-WORST = {}                                  # quantity -> worst error / bound over this module (printed at the end)
-
-
-def L():
-    return _lib.lib()
-
-
-def sync():
-    torch.cuda.synchronize()
-
-
-def st():
-    return _lib.stream()
+WORST = Worst("test_hip_bn.py", ratio_fn=B.worst_ratio)      # quantity -> worst error / bound over this module
+note = WORST.note
 
 
 @pytest.fixture(scope="module", autouse=True)
 def report():
     yield
-    print("\nworst error / bound over test_hip_bn.py: " + ", ".join(f"{k} {v:.3f}" for k, v in WORST.items()))
-
-
-class Buf:
-    """A device buffer of `shape` in the middle of an allocation with PADB guard bytes on either side; the inside is
-    filled with `fill` bytes (0xFF: a NaN in fp32 and bf16, so an element the launch did not write shows) or with `data`."""
-
-    def __init__(self, shape, dtype=torch.float32, data=None, fill=0xFF):
-        self.shape, self.dtype, self.slack_from = tuple(shape), dtype, None
-        self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        room = -(-self.nbytes // 16) * 16
-        self.raw = torch.full((2 * PADB + room,), GUARD, dtype=torch.uint8, device=DEV)
-        self.raw[PADB:PADB + self.nbytes].fill_(fill)
-        self.t = self.raw[PADB:PADB + self.nbytes].view(dtype).view(self.shape)
-        if data is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(data)).to(dtype).view(self.shape))
-        assert self.t.data_ptr() % 16 == 0
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def intact(self):
-        sync()
-        ok = bool((self.raw[:PADB] == GUARD).all()) and bool((self.raw[PADB + self.nbytes:] == GUARD).all())
-        if self.slack_from is not None:          # a workspace: the bytes no kernel has a use for keep their poison
-            ok = ok and bool((self.t[self.slack_from:] == 0xFF).all())
-        return ok
-
-    def np(self):
-        """Values as float64-convertible numpy (bf16 widened exactly to fp32)."""
-        sync()
-        t = self.t.float() if self.dtype == torch.bfloat16 else self.t
-        return t.cpu().numpy().copy()
-
-    def bits(self):
-        sync()
-        kind = {2: torch.int16, 4: torch.int32, 8: torch.int64, 1: torch.uint8}[self.t.element_size()]
-        return self.t.view(kind).cpu().numpy().copy()
-
-
-def P(b):
-    return None if b is None else b.ptr
-
-
-def guards(*bufs):
-    for b in bufs:
-        assert b is None or b.intact(), "a launch wrote outside its buffer"
+    WORST.report()
 
 
 def workspace(R, C, G):
@@ -124,19 +55,6 @@ def rne_bf16_bits(buf):
     """Bits of the round-to-nearest-even bf16 of an fp32 buffer."""
     sync()
     return buf.t.to(torch.bfloat16).view(torch.int16).cpu().numpy()
-
-
-def note(key, got, ref, tol, what, skip=None):
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    tol = np.broadcast_to(tol, ref.shape)
-    if skip is not None:
-        keep = ~np.broadcast_to(skip, ref.shape)
-        got, ref, tol = got[keep], ref[keep], tol[keep]
-    r, i = B.worst_ratio(got, ref, tol)
-    WORST[key] = max(WORST.get(key, 0.0), r)
-    assert r <= 1.0, (f"{what}: {key} at flat index {i}: {got.reshape(-1)[i]!r}, reference {ref.reshape(-1)[i]!r}, "
-                      f"bound {tol.reshape(-1)[i]:.3g}, error / bound = {r:.3f}")
-    return r
 
 
 class Ctx:
@@ -323,7 +241,7 @@ def test_finalize_alone_on_host_partials(chunks):
                 yk = yk.reshape(chunks, 64, C)
                 part[:, k, :, 0], part[:, k, :, 1] = yk.sum(1), (yk * yk).sum(1)
             ws = workspace(R, C, G)
-            ws.t[:part.size * 8].copy_(torch.from_numpy(part.reshape(-1)).view(torch.uint8).to(DEV))
+            ws.t[:part.size * 8].copy_(torch.from_numpy(part.reshape(-1)).view(torch.uint8).to(ws.t.device))
             rm0, rv0 = rs.uniform(-1, 1, C).astype(np.float32), rs.uniform(0.5, 1.5, C).astype(np.float32)
             rm, rv, nbt = Buf((C,), data=rm0), Buf((C,), data=rv0), Buf((1,), torch.int64, data=np.array([3], np.int64))
             first = None

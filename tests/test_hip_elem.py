@@ -9,127 +9,30 @@ must match bit for bit, a lost or doubled term changes the integer) and R (full 
 log-variances over [-30, 30], lv and mu at exactly 0, half-ulp neighbours of 0, x == recon ties, differences of one ulp,
 a denormal difference, -0.0).  No NaN or Inf goes into an arithmetic kernel.
 
-Every buffer a launch may write lies inside an allocation with 256 guard bytes on either side and is filled with 0xFF before
-the launch (an unwritten element is a NaN); the guards must keep their bits.  Every padding region an entry point must not
+Every buffer a launch may write is a guarded one of tests/kernel_harness.py; every padding region an entry point must not
 read holds NaN.  The worst error / bound per kernel and quantity over the module is printed at its end.
 """
 import ctypes
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import assert_same_bits, Buf, EINVAL, F32, F64, guards, L, ok, P, st, Worst
 import dvae_amd  # noqa: E402,F401
 from dvae_amd import _lib  # noqa: E402
 import elem_ref as E  # noqa: E402
 
-DEV = "cuda"
-PADB = 256                                  # guard bytes on either side of every buffer
-GUARD = 0xA5
-EINVAL = -1
-F32, F64 = np.float32, np.float64
 ACTS = {"none": E.ACT_NONE, "relu": E.ACT_RELU, "tanh": E.ACT_TANH}
-WORST = {}                                  # kernel / quantity -> worst error / bound over this module
-TORCH_OF = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8,
-            np.dtype(np.float64): torch.float64, np.dtype(np.uint32): torch.int32}
-
-
-def L():
-    return _lib.lib()
-
-
-def sync():
-    torch.cuda.synchronize()
-
-
-def st():
-    return _lib.stream()
+WORST = Worst("test_hip_elem.py", sort=True, ratio_fn=E.worst_ratio)      # kernel / quantity -> worst error / bound
+note = WORST.note
 
 
 @pytest.fixture(scope="module", autouse=True)
 def report():
     yield
-    print("\nworst error / bound over test_hip_elem.py: " + ", ".join(f"{k} {v:.3f}" for k, v in sorted(WORST.items())))
-
-
-class Buf:
-    """A device buffer of `shape` in the middle of an allocation with PADB guard bytes on either side; the inside is
-    filled with `fill` bytes (0xFF: a NaN in fp32 and bf16, so an element the launch did not write shows) or with `data`
-    (a numpy array: its BITS are uploaded)."""
-
-    def __init__(self, shape, dtype=torch.float32, data=None, fill=0xFF):
-        if data is not None:
-            data = np.ascontiguousarray(data)
-            shape, dtype = data.shape, (TORCH_OF[data.dtype] if dtype == torch.float32 else dtype)
-        self.shape, self.dtype = tuple(shape), dtype
-        self.nbytes = int(np.prod(self.shape)) * torch.empty((), dtype=dtype).element_size()
-        room = -(-self.nbytes // 16) * 16
-        self.raw = torch.full((2 * PADB + room,), GUARD, dtype=torch.uint8, device=DEV)
-        self.raw[PADB:PADB + self.nbytes].fill_(fill)
-        self.t = self.raw[PADB:PADB + self.nbytes].view(dtype).view(self.shape)
-        if data is not None and self.nbytes:
-            if dtype == torch.bfloat16:
-                self.t.copy_(torch.from_numpy(data.astype(np.float32)).to(torch.bfloat16))      # exact: bf16-representable data
-            else:
-                self.raw[PADB:PADB + self.nbytes].copy_(torch.from_numpy(data.reshape(-1).view(np.uint8)))
-        assert self.t.data_ptr() % 16 == 0
-
-    @property
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def intact(self):
-        sync()
-        return bool((self.raw[:PADB] == GUARD).all()) and bool((self.raw[PADB + self.nbytes:] == GUARD).all())
-
-    def np(self):
-        sync()
-        t = self.t.float() if self.dtype == torch.bfloat16 else self.t
-        return t.cpu().numpy().copy()
-
-    def bits(self):
-        sync()
-        kind = {2: torch.int16, 4: torch.int32, 8: torch.int64, 1: torch.uint8}[self.t.element_size()]
-        return self.t.view(kind).cpu().numpy().copy()
-
-
-def P(b):
-    return None if b is None else b.ptr
-
-
-def guards(*bufs):
-    for b in bufs:
-        assert b is None or b.intact(), "a launch wrote outside its buffer"
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F32).view(np.int32)
-
-
-def same_bits(got, ref, what):
-    """got: a Buf, or fp32 values downloaded from one; ref: fp32 values whose bits it must hold."""
-    g_, r_ = (got.bits() if isinstance(got, Buf) else bits(got)).reshape(-1), bits(ref).reshape(-1)
-    bad = np.nonzero(g_ != r_)[0]
-    assert g_.shape == r_.shape and not bad.size, (f"{what}: {bad.size} of {r_.size} elements differ in their bits, first at {bad[:1]}: "
-                                                    f"{g_[bad[:1]].view(F32)} instead of {r_[bad[:1]].view(F32)}")
-
-
-def note(key, got, ref, tol, what):
-    got, ref = np.asarray(got, F64), np.asarray(ref, F64)
-    r, i = E.worst_ratio(got, ref, np.broadcast_to(tol, ref.shape))
-    WORST[key] = max(WORST.get(key, 0.0), r)
-    assert r <= 1.0, (f"{what}: {key} at flat index {i}: {got.reshape(-1)[i]!r}, reference {ref.reshape(-1)[i]!r}, "
-                      f"bound {np.broadcast_to(tol, ref.shape).reshape(-1)[i]:.3g}, error / bound = {r:.3f}")
-
-
-def ok(rc):
-    assert rc == 0, f"return code {rc}, hipError {L().dvae_last_hip_error()}"
+    WORST.report()
 
 
 # ------------------------------------------------------------------ latent
@@ -152,10 +55,10 @@ def test_latent_fwd_and_bwd(name, with_eps_c):
     fb = E.latent_fwd_bounds(d["style"], d["content"], eps_c_np, d["eps_s"], Bh, S, Cn)
     what = f"latent_fwd {name} eps_c={with_eps_c}"
     for buf, key in ((q_mu, "q_mu"), (q_lv, "q_lv"), (s_mu, "s_mu"), (s_lv, "s_lv")):
-        same_bits(buf, fb[key], f"{what} {key}")
+        assert_same_bits(buf, fb[key], f"{what} {key}")
     note("latent_fwd z", z.np(), fb["z"], fb["tol_z"], what)
     if not with_eps_c:
-        same_bits(z.np()[:, S:], d["content"][:, :Cn], what + " z = mu")
+        assert_same_bits(z.np()[:, S:], d["content"][:, :Cn], what + " z = mu")
     for up, keys in UPSTREAM.items():
         ups = [b[k] if k in keys else None for k in UPSTREAM["all"]]
         ups_np = [d[k] if k in keys else None for k in UPSTREAM["all"]]
@@ -212,12 +115,12 @@ def test_l1_sum_fwd_and_bwd(n):
     dy = Buf((n,))
     ok(L().dvae_l1_sum_bwd(bx.ptr, by.ptr, gout.ptr, dy.ptr, n, float(scale), st()))
     guards(dy)
-    same_bits(dy, E.l1_bwd(x, y, gv, scale, F32), f"l1_bwd n={n}")            # one product, then a select: exact
+    assert_same_bits(dy, E.l1_bwd(x, y, gv, scale, F32), f"l1_bwd n={n}")            # one product, then a select: exact
     xe, ye = E.int_pair(rs, n)
     xe[n - 1], ye[n - 1] = 4, -4
     bxe, bye = Buf(None, data=xe), Buf(None, data=ye)
     oe = l1_sum(bxe, bye, n, F32(1 / 64))
-    same_bits(oe, F32([E.l1_fwd(xe, ye, F32(1 / 64))]), f"l1 class E n={n}")
+    assert_same_bits(oe, F32([E.l1_fwd(xe, ye, F32(1 / 64))]), f"l1 class E n={n}")
 
 
 # ------------------------------------------------------------------ the fused loss
@@ -334,7 +237,7 @@ def test_loss_l1_entries_are_exact_on_integers(n):
     d = E.loss_inputs(n, 1, 1, "E", n % 1000)
     b = {k: Buf(None, data=d[k]) for k in E.LOSS_KEYS}
     o = loss_fwd(loss_desc(b, d))
-    same_bits(o.np()[1:5], F32(E.loss_fwd(d)[1:5]), f"loss class E n={n}")
+    assert_same_bits(o.np()[1:5], F32(E.loss_fwd(d)[1:5]), f"loss class E n={n}")
 
 
 # ------------------------------------------------------------------ column sums
@@ -368,7 +271,7 @@ def colsum_case(variant, R, C, ld, b16, cls, with_o2, seed):
             if o is None:
                 continue
             if cls == "E":
-                same_bits(o, F32(E.colsum(Xm, C, old)), what)
+                assert_same_bits(o, F32(E.colsum(Xm, C, old)), what)
             else:
                 ref, tol = E.colsum_bounds(Xm, C, old, variant)
                 note(f"colsum {variant}" + (" bf16" if b16 else ""), o.np(), ref, tol, what)
@@ -419,7 +322,7 @@ def slab_case(n, nslab, stride, act, accumulate, cls, seed):
     if act == E.ACT_TANH:
         note("slab_sum tanh", cb.np(), np.tanh(u.astype(F64)), E.tol_tanh(u), what)
     else:
-        same_bits(cb, E.slab_sum_f32(c, slabs, act, accumulate), what)
+        assert_same_bits(cb, E.slab_sum_f32(c, slabs, act, accumulate), what)
     if cls == "E" and act == E.ACT_NONE:                            # ... and the sequential sum is the exact one
         exact = (c.astype(F64) if accumulate else 0.0) + sum(s.astype(F64) for s in slabs)
         assert np.array_equal(cb.np().astype(F64), exact), what
@@ -456,7 +359,7 @@ def test_slab_fold_seventy_entries():
         ok(L().dvae_slab_fold(descs, len(tab), st()))
         for e, (cb, sb) in enumerate(keep):
             guards(cb, sb)
-            same_bits(cb, want[e], f"slab_fold class {cls} entry {e} {tab[e][:3]}")
+            assert_same_bits(cb, want[e], f"slab_fold class {cls} entry {e} {tab[e][:3]}")
 
 
 # ------------------------------------------------------------------ activations
@@ -477,7 +380,7 @@ def test_act_fwd_and_bwd(n, act):
     if a == E.ACT_TANH:
         note("act_fwd tanh", y.np(), np.tanh(u.astype(F64)), E.tol_tanh(u), what)
     else:
-        same_bits(y, np.where(u > 0, u, F32(0)) if a == E.ACT_RELU else u, what + " forward")
+        assert_same_bits(y, np.where(u > 0, u, F32(0)) if a == E.ACT_RELU else u, what + " forward")
     z = y.np()
     zb, dzb, du = Buf(None, data=z), Buf(None, data=dz), Buf((n,))
     ok(L().dvae_act_bwd(dzb.ptr, zb.ptr, du.ptr, n, a, st()))
@@ -485,7 +388,7 @@ def test_act_fwd_and_bwd(n, act):
     if a == E.ACT_TANH:
         note("act_bwd tanh", du.np(), E.act_bwd(dz, z, a), E.tol_act_bwd_tanh(dz, z), what)
     else:
-        same_bits(du, E.act_bwd_f32(dz, z, a), what + " backward")
+        assert_same_bits(du, E.act_bwd_f32(dz, z, a), what + " backward")
     ok(L().dvae_act_bwd(dzb.ptr, zb.ptr, dzb.ptr, n, a, st()))          # dU may alias dZ
     guards(dzb)
     assert np.array_equal(dzb.bits(), du.bits())
@@ -508,11 +411,11 @@ def test_mel_to_frames_and_back(shape):
         ok(L().dvae_mel_to_frames(b1.ptr, P(second), X.ptr, Bh, C, T, 0, st()))
         guards(X)
         want = E.mel_to_frames(x1, x2 if second is not None else None, Bh, C, T)
-        same_bits(X, want, f"mel_to_frames {shape} x2={second is not None}")
+        assert_same_bits(X, want, f"mel_to_frames {shape} x2={second is not None}")
         back = Buf((N, C, T))
         ok(L().dvae_frames_to_mel(X.ptr, back.ptr, N, C, T, st()))
         guards(back)
-        same_bits(back, np.concatenate([x1, x2]) if second is not None else x1, f"frames_to_mel {shape}")
+        assert_same_bits(back, np.concatenate([x1, x2]) if second is not None else x1, f"frames_to_mel {shape}")
     # bf16: finite inputs with exact round-to-nearest-even ties; the bits must be torch's .bfloat16()
     f1 = F32(rs.uniform(-4, 4, (Bh, C, T)))
     tie = (f1.view(np.uint32) & np.uint32(0xFFFF0000)) | np.uint32(0x8000)          # exactly half way between two bf16
@@ -534,27 +437,27 @@ def test_permute_transpose_and_conv_packs():
         xb, o = Buf(None, data=x), Buf((B_, A, C))
         ok(L().dvae_permute_102(xb.ptr, o.ptr, A, B_, C, st()))
         guards(o)
-        same_bits(o, x.transpose(1, 0, 2), f"permute_102 {A}x{B_}x{C}")
+        assert_same_bits(o, x.transpose(1, 0, 2), f"permute_102 {A}x{B_}x{C}")
     for R, C in E.CASES["transpose"]:
         x = rbits(rs, R, C)
         xb, o = Buf(None, data=x), Buf((C, R))
         ok(L().dvae_transpose(xb.ptr, o.ptr, R, C, st()))
         guards(o)
-        same_bits(o, x.T, f"transpose {R}x{C}")
+        assert_same_bits(o, x.T, f"transpose {R}x{C}")
     for Cout, Cin in E.CASES["conv_pack"]:
         W = rbits(rs, Cout, Cin, 5)
         Wb, p, pt = Buf(None, data=W), Buf((5, Cout, Cin)), Buf((5, Cin, Cout))
         ok(L().dvae_conv_pack_w(Wb.ptr, p.ptr, Cout, Cin, st()))
         ok(L().dvae_conv_pack_wt(Wb.ptr, pt.ptr, Cout, Cin, st()))
         guards(p, pt)
-        same_bits(p, E.conv_pack_w(W, Cout, Cin), f"conv_pack_w {Cout}x{Cin}")
-        same_bits(pt, E.conv_pack_wt(W, Cout, Cin), f"conv_pack_wt {Cout}x{Cin}")
+        assert_same_bits(p, E.conv_pack_w(W, Cout, Cin), f"conv_pack_w {Cout}x{Cin}")
+        assert_same_bits(pt, E.conv_pack_wt(W, Cout, Cin), f"conv_pack_wt {Cout}x{Cin}")
         dWp, dW = F32(rs.uniform(-1, 1, (5, Cout, Cin))), F32(rs.uniform(-1, 1, (Cout, Cin, 5)))
         dWp.reshape(-1)[:2], dW.reshape(-1)[0] = [-0.0, 3.0], -0.0
         acc, src = Buf(None, data=dW), Buf(None, data=dWp)
         ok(L().dvae_conv_unpack_add_w(src.ptr, acc.ptr, Cout, Cin, st()))
         guards(acc)
-        same_bits(acc, E.conv_unpack_add_w(dWp, dW, Cout, Cin), f"conv_unpack_add_w {Cout}x{Cin}")
+        assert_same_bits(acc, E.conv_unpack_add_w(dWp, dW, Cout, Cin), f"conv_unpack_add_w {Cout}x{Cin}")
 
 
 def test_gather_crop():
@@ -570,7 +473,7 @@ def test_gather_crop():
     out, ins = Buf((len(utt), C, T)), [Buf(None, data=a) for a in (mels, lens, utt, off)]
     ok(L().dvae_gather_crop(*[i.ptr for i in ins], out.ptr, len(utt), C, T, Lmax, st()))
     guards(out)
-    same_bits(out, E.gather_crop(mels, lens, utt, off, C, T, Lmax), "gather_crop")
+    assert_same_bits(out, E.gather_crop(mels, lens, utt, off, C, T, Lmax), "gather_crop")
 
 
 @pytest.mark.parametrize("Lk", ["0", "T-1", "T", "2T+5"])
@@ -584,7 +487,7 @@ def test_mel_to_chunks_and_chunks_to_mel(Lk):
     out = Buf((n, C, T))
     ok(L().dvae_mel_to_chunks(melb.ptr, out.ptr, C, Lm, T, n, st()))
     guards(out)
-    same_bits(out, E.mel_to_chunks(mel, C, Lm, T), f"mel_to_chunks L={Lm}")
+    assert_same_bits(out, E.mel_to_chunks(mel, C, Lm, T), f"mel_to_chunks L={Lm}")
     lo, hi = F32(0.0), F32(1.0)
     x = F32(rs.uniform(-0.5, 1.5, (n, C, T)))
     x.reshape(-1)[:6] = [lo, hi, np.nextafter(lo, F32(-1)), np.nextafter(hi, F32(2)), np.nextafter(hi, F32(0)), 2.0 ** -149]
@@ -593,12 +496,12 @@ def test_mel_to_chunks_and_chunks_to_mel(Lk):
         o = Buf((C, n * T))
         ok(L().dvae_chunks_to_mel(xb.ptr, o.ptr, n, C, T, float(lo), float(hi), clamp, st()))
         guards(o)
-        same_bits(o, E.chunks_to_mel(x, n, C, T, lo, hi, clamp), f"chunks_to_mel n={n} clamp={clamp}")
+        assert_same_bits(o, E.chunks_to_mel(x, n, C, T, lo, hi, clamp), f"chunks_to_mel n={n} clamp={clamp}")
     raw = rbits(rs, n, C, T)                                          # clamp off moves bits
     rb, o = Buf(None, data=raw), Buf((C, n * T))
     ok(L().dvae_chunks_to_mel(rb.ptr, o.ptr, n, C, T, 0.0, 1.0, 0, st()))
     guards(o)
-    same_bits(o, E.chunks_to_mel(raw, n, C, T, 0, 1, 0), "chunks_to_mel on random bits")
+    assert_same_bits(o, E.chunks_to_mel(raw, n, C, T, 0, 1, 0), "chunks_to_mel on random bits")
 
 
 # ------------------------------------------------------------------ conversion
@@ -614,8 +517,8 @@ def test_conversion_latents(n, m):
     rs_, rc_, t1, t2 = E.conversion_bounds(ss, sc, ts, n, m, S, Cn)
     note("conversion_latents mean", zs.np()[:, :S], rs_[:, :S], t1, f"z_src {n}x{m}")
     note("conversion_latents mean", zc.np()[:, :S], rc_[:, :S], t2, f"z_conv {n}x{m}")
-    same_bits(zs.np()[:, S:], sc[:, :Cn], "z_src content")
-    same_bits(zc.np()[:, S:], sc[:, :Cn], "z_conv content")
+    assert_same_bits(zs.np()[:, S:], sc[:, :Cn], "z_src content")
+    assert_same_bits(zc.np()[:, S:], sc[:, :Cn], "z_conv content")
 
 
 @pytest.mark.parametrize("n", E.CASES["mul_div"])

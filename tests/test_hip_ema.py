@@ -7,69 +7,41 @@ roundings + 2^-126, against the float64 update fed the kernel's OWN float32 w; t
 own, so the two checks compose and neither hides the other.  Exact properties are asserted on the bits: a repeated launch, an
 element with p == e, a skipped step, the exchange.  Sizes reach every path of the sweep: one float4, either side of one
 workgroup trip (256 threads x 2 float4), and a few float4 past one full sweep of the capped grid (2048 workgroups), where the
-grid-stride loop makes a second, ragged trip.  The average and ema_state lie between sentinels that must keep their bits."""
+grid-stride loop makes a second, ragged trip.  The average and ema_state lie in guarded buffers (tests/kernel_harness.py)."""
 import json
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import bits, Buf, DEV, child, dev_equal, down, flat, EINVAL, guards, make_trainer, same_bits
 import dvae_amd  # noqa: E402,F401
 from dvae_amd import _lib  # noqa: E402
 from dvae_amd.optim import FlatAdam  # noqa: E402
 from adam_ref import LR, grad_mixture, params  # noqa: E402
 from ema_ref import TICK_REL, update_bounds, weight_at, worst_ratio  # noqa: E402
 
-DEV = "cuda"
 U, CAP = 2, 2048                              # EMA_U and the grid cap of csrc/elem.hip
 TRIP = 4 * 256 * U                            # elements one workgroup handles per trip
 SWEEP = CAP * TRIP                            # ... and the whole capped grid: 4 194 304
 SIZES = [4, TRIP - 4, TRIP, TRIP + 4, SWEEP + 4 * 259]      # the last: 256 threads with a first float4, 3 with a second
-SENT = -7.5e11
 RESERVED = (11.0, 12.0, 13.0)                 # ema_state[5:8]: never written
-EINVAL = -1
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-def dev_equal(a, b):
-    """bitwise, on the device"""
-    return bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
-
-
-def down(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 # ------------------------------------------------------------------ the three new launches through ctypes
 class Ema:
-    """p, the average and ema_state on the device, the latter two between 8 sentinels on either side."""
+    """p, the average and ema_state on the device, the latter two in guarded buffers, 32 bytes behind a multiple of 256."""
 
     def __init__(self, e, p, decay, warmup, k=0, w=0.0, applied=0.0):
         self.n = int(np.size(e))
-        self.e = torch.full((self.n + 16,), SENT, dtype=torch.float32, device=DEV)
-        self.e[8:8 + self.n] = torch.from_numpy(np.array(e, np.float32))
+        self.e = Buf(data=np.array(e, np.float32).reshape(-1), lead=32)
         self.p = torch.tensor(np.asarray(p, np.float32), device=DEV)
         self.p0 = self.p.clone()
-        self.st = torch.full((8 + 16,), SENT, dtype=torch.float32, device=DEV)
-        self.st[8:16] = torch.tensor([decay, k, w, float(warmup), applied, *RESERVED], dtype=torch.float32)
-        self.e_ptr, self.st_ptr = self.e.data_ptr() + 32, self.st.data_ptr() + 32
+        self.st = Buf(data=np.array([decay, k, w, float(warmup), applied, *RESERVED], np.float32), lead=32)
+        self.e_ptr, self.st_ptr = self.e.ptr, self.st.ptr
 
     def tick(self, skip=None, clip=None):
         assert _lib.lib().dvae_ema_tick(self.st_ptr, None if skip is None else skip.data_ptr(),
@@ -81,11 +53,10 @@ class Ema:
     def read(self):
         torch.cuda.synchronize()
         assert dev_equal(self.p, self.p0), "p was written"
-        e, st = self.e.cpu().numpy(), self.st.cpu().numpy()
-        assert (e[:8] == np.float32(SENT)).all() and (e[8 + self.n:] == np.float32(SENT)).all(), "the average was overrun"
-        assert (st[:8] == np.float32(SENT)).all() and (st[16:] == np.float32(SENT)).all(), "ema_state was overrun"
-        assert tuple(st[13:16]) == RESERVED, "a reserved word of ema_state was written"
-        return e[8:8 + self.n].copy(), st[8:16].copy()
+        guards(self.e, self.st)
+        e, st = self.e.np(), self.st.np()
+        assert tuple(st[5:8]) == RESERVED, "a reserved word of ema_state was written"
+        return e, st
 
 
 @pytest.fixture(scope="module")
@@ -207,16 +178,12 @@ def test_bad_arguments_are_refused_without_touching_memory(draws):
 def test_swap_exchanges_the_bits_and_twice_restores(draws, n):
     a0, b0 = draws[n]["e"].copy(), draws[n]["far"].copy()
     a0[0], b0[0], a0[-1], b0[-1] = np.float32(np.nan), -0.0, np.float32(1e-40), np.float32(-np.inf)     # bits, not values
-    a = torch.full((n + 16,), SENT, dtype=torch.float32, device=DEV)
-    b = torch.full((n + 16,), SENT, dtype=torch.float32, device=DEV)
-    a[8:8 + n], b[8:8 + n] = torch.from_numpy(a0), torch.from_numpy(b0)
+    a, b = Buf(data=a0, lead=32), Buf(data=b0, lead=32)
 
     def swap():
-        assert _lib.lib().dvae_swap_f32(a.data_ptr() + 32, b.data_ptr() + 32, n, _lib.stream()) == 0
-        x, y = down(a), down(b)
-        for t in (x, y):
-            assert (t[:8] == np.float32(SENT)).all() and (t[8 + n:] == np.float32(SENT)).all(), "a buffer was overrun"
-        return x[8:8 + n], y[8:8 + n]
+        assert _lib.lib().dvae_swap_f32(a.ptr, b.ptr, n, _lib.stream()) == 0
+        guards(a, b)
+        return a.np(), b.np()
 
     x, y = swap()
     assert same_bits(x, b0) and same_bits(y, a0)
@@ -248,12 +215,6 @@ def feed(opt, seed):
         p.grad.copy_(torch.from_numpy(grad_mixture(1000 * seed + i, p.numel())).view(p.shape))
         if getattr(p, "_dvae_grad_store_first", False):
             p._dvae_sf_writes = 1                      # written once, as the backward pass of a step does
-
-
-def flat(opt):
-    torch.cuda.synchronize()
-    return {"p": opt.flat_p.cpu().numpy().copy(), "g": opt.flat_g.cpu().numpy().copy(), "m": opt.exp_avg.cpu().numpy().copy(),
-            "v": opt.exp_avg_sq.cpu().numpy().copy()}
 
 
 @pytest.mark.parametrize("warmup", [False, True], ids=["plain", "warm-up"])
@@ -436,15 +397,6 @@ def test_state_dict_carries_the_average_and_load_restores_it():
 
 
 # ------------------------------------------------------------------ the whole step
-def make_trainer(batch=4, n_frames=64, lr=1e-4):
-    from oracle.fill import fill_state_dict
-    w = dvae_amd.ConvolutionalMulVAE("VCTK", n_frames, 80, 32, lr, 0.01, 500, False, batch_size=batch, speaker_size=4,
-                                     device=torch.device("cuda"), latent_dim=32, mse_cof=10, kl_cof=10)
-    w.model.load_state_dict(fill_state_dict(w.model.state_dict()))
-    w.model.train()
-    return w
-
-
 def eval_forward(w, x1, x2, eps):
     w.model.eval()
     w.model.eps_override = eps
@@ -566,18 +518,6 @@ EMA_KEYS = {"EMA/Updates", "EMA/Weight"}
 BASE = "DisentangledVAE_VCTK_2"
 
 
-def _child(module, argv, ok=True):
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    code = {"train": "import dvae_amd.train as t, sys; t.main(sys.argv[1:])",
-            "probe": "import dvae_amd.probe as t, sys; sys.exit(t.main(sys.argv[1:]))"}[module]
-    cmd = [sys.executable, "-c", code] + [str(a) for a in argv]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)      # a fresh child, under a time limit
-    if ok:
-        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
-    return r
-
-
 @pytest.fixture(scope="module")
 def cli_runs(tmp_path_factory):
     """Two training runs of the command line on one synthetic corpus, shared by the tests below: two epochs of four steps
@@ -591,7 +531,7 @@ def cli_runs(tmp_path_factory):
     out = {"corpus": corpus, "common": common}
     for name, extra in (("ema", ["--ema-decay", "0.9", "--convert", "true"]), ("plain", [])):
         log_dir = root / name
-        _child("train", ["--train", "true", "--do-not-resume", f"--log_dir={log_dir}"] + common + extra)
+        child("train", ["--train", "true", "--do-not-resume", f"--log_dir={log_dir}"] + common + extra)
         out[name] = log_dir
     return out
 
@@ -644,11 +584,11 @@ def test_convert_use_ema_voices_the_average(cli_runs):
     last = np.load(mel)
     assert wav.is_file() and np.isfinite(last).all()
     os.remove(wav)
-    _child("train", ["--convert", "true", "--use-ema", f"--log_dir={cli_runs['ema']}"] + cli_runs["common"])
+    child("train", ["--convert", "true", "--use-ema", f"--log_dir={cli_runs['ema']}"] + cli_runs["common"])
     averaged = np.load(mel)
     assert wav.is_file() and wav.stat().st_size > 44
     assert averaged.shape == last.shape and np.isfinite(averaged).all() and not np.array_equal(averaged, last)
-    r = _child("train", ["--convert", "true", "--use-ema", f"--log_dir={cli_runs['plain']}"] + cli_runs["common"], ok=False)
+    r = child("train", ["--convert", "true", "--use-ema", f"--log_dir={cli_runs['plain']}"] + cli_runs["common"], ok=False)
     assert r.returncode != 0 and BASE + ".ema.pth" in r.stderr, (r.returncode, r.stderr[-2000:])
     assert not (cli_runs["plain"] / "generation" / "spk000_to_spk001" / "convert_spk000_to_spk001_utt000.npy").exists()
 
@@ -656,9 +596,9 @@ def test_convert_use_ema_voices_the_average(cli_runs):
 def test_probe_use_ema(cli_runs):
     out = cli_runs["ema"] / "probe_ema.json"
     args = [cli_runs["corpus"], "--log_dir", cli_runs["ema"], "--epochs", 2, "--seed", 1]
-    _child("probe", args + ["--use-ema", "--json", out])
+    child("probe", args + ["--use-ema", "--json", out])
     res = json.loads(out.read_text())
     assert res["use_ema"] is True and res["checkpoint_epoch"] == 2 and set(res["probes"]) == {"style", "content"}
     assert all(0.0 <= res["probes"][k]["held_out_accuracy"] <= 1.0 for k in res["probes"])
-    r = _child("probe", [cli_runs["corpus"], "--log_dir", cli_runs["plain"], "--epochs", 1, "--use-ema"], ok=False)
+    r = child("probe", [cli_runs["corpus"], "--log_dir", cli_runs["plain"], "--epochs", 1, "--use-ema"], ok=False)
     assert r.returncode == 1 and BASE + ".ema.pth" in r.stderr, (r.returncode, r.stderr[-2000:])

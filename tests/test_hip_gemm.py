@@ -11,8 +11,6 @@ that moves a case to another kernel fails here instead of passing vacuously.  Ar
 ldc > N, the guard elements in front of and behind C, the slabs behind the used ones and C itself under a split slab launch
 keep their poison.  The worst error / bound per kernel family and class is printed at the module's end."""
 import ctypes as C
-import os
-import sys
 import time
 
 import numpy as np
@@ -20,32 +18,18 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import DEV, L, ok, st      # first: it puts the repository root on sys.path
 import dvae_amd  # noqa: E402,F401
 from dvae_amd import _lib, ops  # noqa: E402
 import gemm_ref as G  # noqa: E402
 
-DEV = "cuda"
 F = np.float32
 POISON = -1.2345678e30                      # what untouched memory holds
-GUARD = 8                                   # guard elements on either side of C
+GUARD = 136                                 # guard elements on either side of C: at least 256 bytes in fp32 and bf16, and
+                                            # 8 elements behind a multiple of 256 bytes, so C keeps the offset it had
 WORST = {}                                  # (kernel family, class) -> worst error / bound (exact classes: 0 = every bit held)
 RHO = {}
 T0 = time.time()
-
-
-def L():
-    return _lib.lib()
-
-
-def st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def ok(rc, what):
-    assert rc == 0, f"{what}: rc = {rc} (hip error {L().dvae_last_hip_error() if rc == -2 else 0})"
 
 
 @pytest.fixture(scope="module", autouse=True)

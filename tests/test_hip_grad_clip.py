@@ -7,59 +7,34 @@ gs max_norm / (ref_norm + 1e-6), eff == gs BIT FOR BIT where the coefficient cla
 adam_ref's one-step bounds against the float64 Adam fed the kernel's OWN float32 eff, so the two checks compose and neither
 hides the other.  Sizes reach every path of the reduction: one float4, either side of one workgroup trip (256 threads x 2
 float4), and a few float4 past one full sweep of the capped grid (2048 workgroups), where the grid-stride loop makes a
-second, ragged trip.  The workspace and clip_state lie between sentinels that must keep their bits."""
+second, ragged trip.  The workspace and clip_state lie in guarded buffers (tests/kernel_harness.py)."""
 import json
 import math
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import bits, Buf, DEV, child, dev_equal, down, flat, EINVAL, guards, make_trainer, same_bits
 import dvae_amd  # noqa: E402,F401
 from dvae_amd import _lib  # noqa: E402
 from dvae_amd.optim import FlatAdam  # noqa: E402
 from adam_ref import BETAS, EPS, LR, bias_corrections, grad_mixture, one_step_bounds, params, worst_ratio  # noqa: E402
 from grad_clip_ref import clip_ref, eff_tol, norm_tol, sum_squares  # noqa: E402
 
-DEV = "cuda"
 U, CAP = 2, 2048                              # SUMSQ_U, SUMSQ_CAP of csrc/elem.hip
 TRIP = 4 * 256 * U                            # elements one workgroup reads per trip
 SWEEP = CAP * TRIP                            # ... and the whole capped grid: 4 194 304
 SIZES = [4, TRIP - 4, TRIP, TRIP + 4, SWEEP + 4 * 259]      # the last: 256 threads with a first float4, 3 with a second
 SENT = -7.5e11
 B1F, B2F, EPSF, LRF = (np.float32(x) for x in (BETAS[0], BETAS[1], EPS, LR))
-EINVAL = -1
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-def dev_equal(a, b):
-    """bitwise, on the device"""
-    return bool(torch.equal(a.view(torch.int32), b.view(torch.int32)))
-
-
-def down(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
 
 
 # ------------------------------------------------------------------ the two new launches through ctypes
 class Clip:
-    """g, the float64 workspace and clip_state on the device, the latter two between 8 sentinels on either side."""
+    """g, the float64 workspace and clip_state on the device, the latter two in guarded buffers, 64 and 32 bytes behind a
+    multiple of 256; the workspace starts as the sentinel."""
 
     def __init__(self, g, gs, max_norm):
         L = _lib.lib()
@@ -68,23 +43,20 @@ class Clip:
         self.g0 = self.g.clone()
         self.nws = int(L.dvae_grad_sumsq_ws_bytes(self.n)) // 8
         assert self.nws == min(CAP, max(1, -(-(self.n // 4) // (256 * U)))), (self.n, self.nws)
-        self.ws = torch.full((self.nws + 16,), SENT, dtype=torch.float64, device=DEV)
-        self.clip = torch.full((8 + 16,), SENT, dtype=torch.float32, device=DEV)
-        self.clip[8:16] = torch.tensor([max_norm, 0, 0, 0, 0, 0, 0, 0], dtype=torch.float32)
+        self.ws = Buf(data=np.full(self.nws, SENT, np.float64), lead=64)
+        self.clip = Buf(data=np.array([max_norm, 0, 0, 0, 0, 0, 0, 0], np.float32), lead=32)
         self.state = torch.tensor([3, 0.271, 0.0547, SENT, float(LRF), gs, SENT, SENT], dtype=torch.float32, device=DEV)
         self.state0 = self.state.clone()
 
     def run(self, guard=1, skip=None):
         L = _lib.lib()
-        assert L.dvae_grad_sumsq(self.g.data_ptr(), self.n, self.ws.data_ptr() + 64, _lib.stream()) == 0
-        assert L.dvae_grad_clip_finalize(self.ws.data_ptr() + 64, self.n, self.state.data_ptr(), self.clip.data_ptr() + 32,
+        assert L.dvae_grad_sumsq(self.g.data_ptr(), self.n, self.ws.ptr, _lib.stream()) == 0
+        assert L.dvae_grad_clip_finalize(self.ws.ptr, self.n, self.state.data_ptr(), self.clip.ptr,
                                          None if skip is None else skip.data_ptr(), guard, _lib.stream()) == 0
         torch.cuda.synchronize()
         assert dev_equal(self.g, self.g0) and dev_equal(self.state, self.state0)          # read-only inputs
-        ws, clip = self.ws.cpu().numpy(), self.clip.cpu().numpy()
-        assert (ws[:8] == SENT).all() and (ws[8 + self.nws:] == SENT).all(), "the workspace was overrun"
-        assert (clip[:8] == np.float32(SENT)).all() and (clip[16:] == np.float32(SENT)).all(), "clip_state was overrun"
-        return clip[8:16].copy(), ws[8:8 + self.nws].copy()
+        guards(self.ws, self.clip)
+        return self.clip.np(), self.ws.np()
 
 
 @pytest.fixture(scope="module")
@@ -157,8 +129,8 @@ def test_finalize_honours_the_skip_word_and_refuses_bad_arguments(draws):
     out, _ = c.run(skip=word)
     assert out[1] > 0 and out[6] == 1
     L, st = _lib.lib(), _lib.stream()
-    ws, clip, state = c.ws.data_ptr() + 64, c.clip.data_ptr() + 32, c.state.data_ptr()
-    before = down(c.clip)
+    ws, clip, state = c.ws.ptr, c.clip.ptr, c.state.data_ptr()
+    before = c.clip.np()
     assert L.dvae_grad_sumsq_ws_bytes(0) == 0 and L.dvae_grad_sumsq_ws_bytes(6) == 0
     for args in ((None, c.n, ws, st), (c.g.data_ptr(), 0, ws, st), (c.g.data_ptr(), 6, ws, st), (c.g.data_ptr(), c.n, None, st),
                  (c.g.data_ptr() + 4, c.n - 4, ws, st), (c.g.data_ptr(), c.n, ws + 4, st)):
@@ -167,7 +139,8 @@ def test_finalize_honours_the_skip_word_and_refuses_bad_arguments(draws):
         assert L.dvae_grad_clip_finalize(*args, None, 1, st) == EINVAL, args
     a = [c.g.data_ptr()] * 4
     assert L.dvae_adam_flat_dev_clip(*a, c.n, 0.9, 0.999, 1e-8, state, None, None, 1, None, st) == EINVAL
-    assert same_bits(before, down(c.clip))
+    guards(c.ws, c.clip)
+    assert same_bits(before, c.clip.np())
 
 
 # ------------------------------------------------------------------ FlatAdam with clipping on
@@ -193,12 +166,6 @@ def feed(opt, seed, scale=1.0):
         if getattr(p, "_dvae_grad_store_first", False):
             p._dvae_sf_writes = 1                      # written once, as the backward pass of a step does
     return down(opt.flat_g)
-
-
-def flat(opt):
-    torch.cuda.synchronize()
-    return {"p": opt.flat_p.cpu().numpy().copy(), "g": opt.flat_g.cpu().numpy().copy(), "m": opt.exp_avg.cpu().numpy().copy(),
-            "v": opt.exp_avg_sq.cpu().numpy().copy()}
 
 
 def zero_mask(opt):
@@ -382,15 +349,6 @@ def test_max_norm_is_a_device_scalar_and_capture_needs_it_sent(monkeypatch):
 
 
 # ------------------------------------------------------------------ the whole step
-def make_trainer(batch=4, n_frames=64, lr=1e-4):
-    from oracle.fill import fill_state_dict
-    w = dvae_amd.ConvolutionalMulVAE("VCTK", n_frames, 80, 32, lr, 0.01, 500, False, batch_size=batch, speaker_size=4,
-                                     device=torch.device("cuda"), latent_dim=32, mse_cof=10, kl_cof=10)
-    w.model.load_state_dict(fill_state_dict(w.model.state_dict()))
-    w.model.train()
-    return w
-
-
 def test_replayed_graph_equals_eager_step_with_clipping_on():
     """config 0 at B = 4 / T = 64: the first step measures (max_norm = inf), then max_norm = 5 % of that norm so that every
     step clips; four steps, graph against eager, bit for bit.  Then max_norm changes under the SAME graph, and switching
@@ -503,14 +461,10 @@ GRAD_KEYS = {"Grad/Norm mean", "Grad/Norm max", "Grad/Clipped steps", "Grad/Skip
 def _cli(tmp_path, name, extra):
     from dvae_amd.data import write_synthetic_corpus
     corpus = write_synthetic_corpus(str(tmp_path / "corpus"), n_speakers=2, n_utt=16, length=96, seed=0)   # 16 pairs
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     log_dir = tmp_path / name
-    cmd = [sys.executable, "-c", "import dvae_amd.train as t, sys; t.main(sys.argv[1:])", "--train", "true",
-           f"--dataset_fp={corpus}", "--batch-size=4", "--latent-size=32", "--speaker_size=4", "--lr=1e-4", "--epochs=2",
-           "--report-interval=2", "--mse_cof=10", "--kl_cof=10", f"--log_dir={log_dir}", "--seed=3", "--do-not-resume"] + extra
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)      # a fresh child, under a time limit
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    child("train", ["--train", "true", f"--dataset_fp={corpus}", "--batch-size=4", "--latent-size=32", "--speaker_size=4", "--lr=1e-4",
+                    "--epochs=2", "--report-interval=2", "--mse_cof=10", "--kl_cof=10", f"--log_dir={log_dir}", "--seed=3",
+                    "--do-not-resume"] + extra)
     recs = [json.loads(line) for line in open(log_dir / "logs" / "DisentangledVAE_VCTK" / "scalars.jsonl")]
     return recs, json.load(open(log_dir / "config.json"))
 

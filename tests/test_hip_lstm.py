@@ -8,100 +8,38 @@ H % 512 == 0 are stepped through dvae_lstm_seq_bwd_range and dc_ws is read after
 in tests/lstm_ref.py, per element, never a fraction of a tensor's maximum; 100 % of the elements are compared.  The cases
 are `lstm_ref.CASES`: tests/test_lstm_ref.py asserts which kernel each of them reaches.
 
-Every buffer a launch may write lies inside a larger allocation with 256 guard bytes on either side and is filled with 0xFF
-before the launch (an unwritten element is a NaN); the guards must keep their bits.  Where two directions write columns of
-one tensor, one direction is also run alone and the other one's columns must keep their poison.  A bf16-stored h or dG is
-held through its bound and, besides, to the same case run with fp32 storage (2^-8 relative plus the fp32 bound: in the bf16
+Every buffer a launch may write is a guarded one of tests/kernel_harness.py.  Where two directions write columns of one
+tensor, one direction is also run alone and the other one's columns must keep their poison.  A bf16-stored h or dG is held
+through its bound and, besides, to the same case run with fp32 storage (2^-8 relative plus the fp32 bound: in the bf16
 mode both runs feed the next frame the same rounded operand).  The whole-sequence kernels (H = 64, persistent) keep the
 cell-gradient carry in registers and never store dc_ws: there it must keep its poison.  The worst error / bound per kernel
 family and quantity is printed at the module's end.
 """
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import Buf, DEV, guards, L, Worst      # first: it puts the repository root on sys.path
 import dvae_amd  # noqa: E402,F401
 from dvae_amd import _lib, ops  # noqa: E402
 from dvae_amd.derived import lstm_local  # noqa: E402
 import lstm_ref as R  # noqa: E402
 
-DEV = "cuda"
-PADB = 256                                  # guard bytes on either side of every buffer
-GUARD = 0xA5
-WORST = {}                                  # (kernel family, quantity) -> worst error / bound over this module
+WORST = Worst("test_hip_lstm.py")              # (kernel family, quantity) -> worst error / bound over this module
 FP32_STORED = {}                            # case with fp32 storage -> per entry (h, dG, their bounds): the bf16-stored twin reads it
-
-
-def L():
-    return _lib.lib()
-
-
-def sync():
-    torch.cuda.synchronize()
 
 
 @pytest.fixture(scope="module", autouse=True)
 def report():
     yield
-    fams = sorted({f for f, _ in WORST})
-    keys = []
-    for _, k in WORST:
-        if k not in keys:
-            keys.append(k)
-    print("\nworst error / bound over test_hip_lstm.py\n| kernels | " + " | ".join(keys) + " |\n|---|" + "---|" * len(keys))
-    for f in fams:
-        print(f"| {f} | " + " | ".join(f"{WORST[(f, k)]:.3f}" if (f, k) in WORST else "" for k in keys) + " |")
-
-
-class Buf:
-    """A device buffer of `shape` in the middle of an allocation with PADB guard bytes on either side; the inside is filled
-    with 0xFF bytes (a NaN in fp32 and bf16: an element the launch did not write shows) or with `data`."""
-
-    def __init__(self, shape, dtype=torch.float32, data=None):
-        self.shape, self.dtype = tuple(shape), dtype
-        self.esize = torch.empty((), dtype=dtype).element_size()
-        self.nbytes = int(np.prod(shape)) * self.esize
-        room = -(-self.nbytes // 16) * 16
-        self.raw = torch.full((2 * PADB + room,), GUARD, dtype=torch.uint8, device=DEV)
-        self.raw[PADB:PADB + self.nbytes].fill_(0xFF)
-        self.t = self.raw[PADB:PADB + self.nbytes].view(dtype).view(self.shape)
-        if data is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(data)).to(dtype).view(self.shape))
-        assert self.t.data_ptr() % 16 == 0
-
-    def ptr(self, elem_offset=0):
-        return self.t.data_ptr() + elem_offset * self.esize
-
-    def intact(self):
-        sync()
-        return bool((self.raw[:PADB] == GUARD).all()) and bool((self.raw[PADB + self.nbytes:] == GUARD).all())
-
-    def np(self):
-        """Values as numpy fp32 (bf16 widened exactly)."""
-        sync()
-        return self.t.float().cpu().numpy().copy()
-
-    def poisoned(self):
-        """Per element: still the 0xFF fill."""
-        sync()
-        return (self.t.contiguous().view(torch.uint8).view(*self.shape, self.esize) == 0xFF).all(-1).cpu().numpy()
-
-
-def guards(*bufs):
-    for b in bufs:
-        assert b is None or b.intact(), "a launch wrote outside its buffer"
+    WORST.report()
 
 
 def note(fam, res, what):
     for k, (r, where) in res.items():
-        WORST[(fam, k)] = max(WORST.get((fam, k), 0.0), r)
+        WORST.record((fam, k), r)
     for k, (r, where) in res.items():
         assert r <= 1.0, f"{what}: {k}: error / bound = {r:.3f} at {where}"
 
@@ -137,9 +75,9 @@ class Layer:
         if side_by_side:
             assert self.n == 2
             b = Buf((T, N, 2 * width), dtype, None if data is None else np.concatenate(data, 2))
-            return [b], [b.ptr(0), b.ptr(width)]
+            return [b], [b.ptr, b.at(width)]
         bufs = [Buf((T, N, width), dtype, None if data is None else data[i]) for i in range(self.n)]
-        return bufs, [b.ptr() for b in bufs]
+        return bufs, [b.ptr for b in bufs]
 
     def cols(self, bufs, side_by_side, width, i):
         """Entry i's [T, N, width] of what `shared` made, as numpy."""
@@ -149,7 +87,7 @@ class Layer:
         c = self.c
         d = (_lib.LstmDir * len(which))()
         for k, i in enumerate(which):
-            d[k].gates, d[k].w_hh, d[k].h_out, d[k].c_all = gptr[i], _lib.ptr(self.w[i]), hptr[i], self.cbuf[i].ptr()
+            d[k].gates, d[k].w_hh, d[k].h_out, d[k].c_all = gptr[i], _lib.ptr(self.w[i]), hptr[i], self.cbuf[i].ptr
             d[k].w_packed = _lib.ptr(self.der[i].pack_f)
             d[k].reverse, d[k].packed_mode, d[k].step_shift, d[k].state_bf16 = c.rev[i], c.mode, c.shifts[i], c.st16
             d[k].gate_ld = self.ldg if c.gld2 else 0
@@ -199,21 +137,21 @@ class Layer:
                 assert L().dvae_lstm_pack_w(_lib.ptr(self.w[i]), None, _lib.ptr(packs[i]), H, _lib.stream()) == 0
         db = dbp = None
         if bias == "ih_hh":
-            db = Buf((2, 4 * H), data=self.ent[0]["db0"])
+            db = Buf((2, 4 * H), torch.float32, self.ent[0]["db0"])
         elif bias == "part":
             dbp = Buf((_lib.PERS_BIAS_SLABS, 4 * H))
         d = (_lib.LstmDir * self.n)()
         for i in range(self.n):
-            d[i].gates, d[i].c_all, d[i].w_hh, d[i].w_packed = self.gptr[i], self.cbuf[i].ptr(), _lib.ptr(self.der[i].w_hh_t), _lib.ptr(packs[i])
-            d[i].dh_out, d[i].dgates, d[i].dc_ws = dhptr[i], dgptr[i], dc[i].ptr()
+            d[i].gates, d[i].c_all, d[i].w_hh, d[i].w_packed = self.gptr[i], self.cbuf[i].ptr, _lib.ptr(self.der[i].w_hh_t), _lib.ptr(packs[i])
+            d[i].dh_out, d[i].dgates, d[i].dc_ws = dhptr[i], dgptr[i], dc[i].ptr
             d[i].reverse, d[i].packed_mode, d[i].step_shift, d[i].state_bf16 = c.rev[i], bmode, c.shifts[i], int(g16)
             d[i].gate_ld = self.ldg if c.gld2 else 0
             if pers:
                 d[i].pers_ws = _lib.ptr(ops.lstm_pers_workspace(DEV))
                 if db is not None:
-                    d[i].dbias_ih, d[i].dbias_hh = db.ptr(0), db.ptr(4 * H)
+                    d[i].dbias_ih, d[i].dbias_hh = db.ptr, db.at(4 * H)
                 if dbp is not None:
-                    d[i].dbias_part = dbp.ptr()
+                    d[i].dbias_part = dbp.ptr
         steps = None
         if stepped:
             steps = [[] for _ in range(self.n)]

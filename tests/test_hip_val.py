@@ -7,64 +7,29 @@ tests/val_ref.py, none is fitted."""
 import ctypes
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_harness import Buf, child, DEV, dev_equal, down, EINVAL, F32, F64, guards, L, make_trainer, st
 import dvae_amd  # noqa: E402,F401
 from dvae_amd import _lib, data, ops  # noqa: E402
 import elem_ref as E  # noqa: E402
 import val_ref as V  # noqa: E402
 
-DEV = "cuda"
 SENT = -7.5e11
-EINVAL = -1
-F32, F64 = np.float32, np.float64
 
 
-def L():
-    return _lib.lib()
+def guarded(data, dtype=torch.float32):
+    """`data` in a guarded buffer whose payload lies 64 bytes behind a multiple of 256."""
+    return Buf(dtype=dtype, data=np.asarray(data), lead=64)
 
 
-def st():
-    return _lib.stream()
-
-
-def down(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy().copy()
-
-
-def dev_equal(a, b):
-    return a.shape == b.shape and bool(torch.equal(a.contiguous().reshape(-1).view(torch.uint8), b.contiguous().reshape(-1).view(torch.uint8)))
-
-
-class Guarded:
-    """A device buffer between 64 sentinel bytes on either side (16-byte aligned payload)."""
-
-    def __init__(self, shape, dtype=torch.float32, fill=None):
-        self.shape, self.dtype = tuple(shape), dtype
-        self.nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        pad = -self.nbytes % 16
-        self.raw = torch.full((64 + self.nbytes + pad + 64,), 0xA5, dtype=torch.uint8, device=DEV)
-        self.ptr = self.raw.data_ptr() + 64
-        if fill is not None:
-            self.view().copy_(torch.as_tensor(fill, dtype=dtype).reshape(self.shape))
-
-    def view(self):
-        return self.raw[64:64 + self.nbytes].view(self.dtype).view(self.shape)
-
-    def read(self):
-        r = down(self.raw)
-        assert (r[:64] == 0xA5).all() and (r[64 + self.nbytes:] == 0xA5).all(), "a buffer was overrun"
-        return down(self.view())
+def read(b):
+    guards(b)
+    return b.np()
 
 
 def launch_pair(dev, out, Bh, n_per, D, S, mse, kl, shift=0):
@@ -85,9 +50,9 @@ def test_pair_metrics_against_float64_loss_fwd_and_itself(n_per, Bh):
             ref, tol = V.pair_bounds(*[d[k] for k in V.KEYS], mse, kl)
             outs = []
             for _ in range(2):
-                out = Guarded((Bh, 8), fill=np.full((Bh, 8), SENT, F32))
+                out = guarded(np.full((Bh, 8), SENT, F32))
                 assert launch_pair(dev, out, Bh, n_per, D, S, mse, kl) == 0
-                outs.append(out.read())
+                outs.append(read(out))
             got = outs[0].astype(F64)
             assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))       # a second launch: the same bits
             r = float((np.abs(got - ref) / tol).max())
@@ -113,10 +78,10 @@ def test_pair_metrics_against_float64_loss_fwd_and_itself(n_per, Bh):
             desc.n, desc.nq, desc.ns = n, Bh * D, Bh * S
             for k in E.SCALE_KEYS:
                 setattr(desc, k, float(ld[k]))
-            out8 = Guarded((8,), fill=np.full(8, SENT, F32))
+            out8 = guarded(np.full(8, SENT, F32))
             ws = torch.empty(L().dvae_loss_ws_bytes(n), dtype=torch.uint8, device=DEV)
             assert L().dvae_loss_fwd(ctypes.byref(desc), out8.ptr, ws.data_ptr(), st()) == 0
-            o8 = out8.read().astype(F64)
+            o8 = read(out8).astype(F64)
             _, tol8 = E.loss_fwd_bounds(ld, o8)
             tol8[0] += mse * tol8[1:5].sum() + kl * (tol8[5] + tol8[6])         # out8[0] is bounded from the device's own parts
             both = tol8 + tol.mean(0) + 2 * V.EPS32 * np.abs(o8)                # + the rounding of the fp32 scale 1 / Bh
@@ -139,9 +104,9 @@ def test_pair_metrics_unaligned_operands_take_the_scalar_path():
         else:
             dev[k] = torch.from_numpy(d[k]).to(DEV)
     ref, tol = V.pair_bounds(*[d[k] for k in V.KEYS], 10.0, 10.0)
-    out = Guarded((Bh, 8), fill=np.full((Bh, 8), SENT, F32))
+    out = guarded(np.full((Bh, 8), SENT, F32))
     assert launch_pair(dev, out, Bh, n_per, D, S, 10.0, 10.0, shift=4) == 0
-    r = float((np.abs(out.read().astype(F64) - ref) / tol).max())
+    r = float((np.abs(read(out).astype(F64) - ref) / tol).max())
     print(f"unaligned: worst error / bound = {r:.3f}")
     assert r <= 1.0
 
@@ -150,7 +115,7 @@ def test_pair_metrics_bad_arguments_write_nothing():
     Bh, n_per, D, S = 2, 8, 4, 2
     d = V.pair_inputs(Bh, n_per, D, S, seed=5)
     dev = {k: torch.from_numpy(d[k]).to(DEV) for k in V.KEYS}
-    out = Guarded((Bh, 8), fill=np.full((Bh, 8), SENT, F32))
+    out = guarded(np.full((Bh, 8), SENT, F32))
     ptrs = [dev[k].data_ptr() for k in V.KEYS]
     for i in range(9):
         a = ptrs + [out.ptr]
@@ -158,7 +123,7 @@ def test_pair_metrics_bad_arguments_write_nothing():
         assert L().dvae_pair_metrics(*a, Bh, n_per, D, S, 10.0, 10.0, st()) == EINVAL, i
     for sizes in ((0, n_per, D, S), (-1, n_per, D, S), (Bh, 0, D, S), (Bh, -4, D, S), (Bh, n_per, 0, S), (Bh, n_per, D, 0)):
         assert L().dvae_pair_metrics(*ptrs, out.ptr, *sizes, 10.0, 10.0, st()) == EINVAL, sizes
-    assert (out.read() == F32(SENT)).all()
+    assert (read(out) == F32(SENT)).all()
 
 
 # ------------------------------------------------------------------ dvae_group_sum_f64
@@ -170,8 +135,7 @@ class Sums:
         c0 = np.zeros(G + 1, np.int64) if old is None else rs.randint(0, 9, G + 1)
         b0 = np.zeros(G + 1, np.int64) if old is None else rs.randint(0, 9, G + 1)
         self.host = (s0, c0, b0)
-        self.s, self.c, self.b = Guarded((G + 1, K), torch.float64, s0), Guarded((G + 1,), torch.int64, c0), \
-            Guarded((G + 1,), torch.int64, b0)
+        self.s, self.c, self.b = guarded(s0, torch.float64), guarded(c0, torch.int64), guarded(b0, torch.int64)
 
     def add(self, rows, group):
         r, g = torch.from_numpy(np.ascontiguousarray(rows, F32)).to(DEV), torch.from_numpy(np.asarray(group, np.int32)).to(DEV)
@@ -180,7 +144,7 @@ class Sums:
         self.host = V.group_sum(rows, group, self.G, *self.host)
 
     def check(self):
-        s, c, b = self.s.read(), self.c.read(), self.b.read()
+        s, c, b = read(self.s), read(self.c), read(self.b)
         assert np.array_equal(s.view(np.uint64), self.host[0].view(np.uint64)), "not the sequential float64 sum"
         assert np.array_equal(c, self.host[1]) and np.array_equal(b, self.host[2]), (c, b, self.host[1:])
         return s, c, b
@@ -243,15 +207,6 @@ def test_group_sum_bad_arguments_write_nothing():
 
 # ------------------------------------------------------------------ validate on the trainer
 B, T = 4, 64
-
-
-def make_trainer(lr=1e-4):
-    from oracle.fill import fill_state_dict
-    w = dvae_amd.ConvolutionalMulVAE("VCTK", T, 80, 32, lr, 0.01, 500, False, batch_size=B, speaker_size=4,
-                                     device=torch.device("cuda"), latent_dim=32, mse_cof=10, kl_cof=10)
-    w.model.load_state_dict(fill_state_dict(w.model.state_dict()))
-    w.model.train()
-    return w
 
 
 class FixedPairs:
@@ -453,16 +408,6 @@ def test_a_run_that_validates_trains_exactly_as_one_that_does_not(corpus, graph)
 
 
 # ------------------------------------------------------------------ the command line
-def _child(argv, ok=True):
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
-    cmd = [sys.executable, "-c", "import dvae_amd.train as t, sys; t.main(sys.argv[1:])"] + [str(a) for a in argv]
-    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)      # a fresh child, under a time limit
-    if ok:
-        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
-    return r
-
-
 @pytest.fixture(scope="module")
 def cli_runs(tmp_path_factory):
     """Two training runs of the command line on one synthetic corpus: two epochs with --val-fraction 0.25 --ema-decay 0.9
@@ -476,7 +421,7 @@ def cli_runs(tmp_path_factory):
     out = {"corpus": corpus, "common": common}
     for name, extra in (("val", ["--val-fraction", "0.25", "--ema-decay", "0.9"]), ("plain", [])):
         out[name] = root / name
-        _child(["--train", "true", "--do-not-resume", f"--log_dir={out[name]}"] + common + extra)
+        child("train", ["--train", "true", "--do-not-resume", f"--log_dir={out[name]}"] + common + extra)
     return out
 
 
@@ -494,13 +439,13 @@ def test_train_cli_validates_and_convert_follows_best_json(cli_runs):
     best = json.load(open(log / "checkpoints" / "best.json"))
     assert best["epoch"] == 2 and (log / "checkpoints" / best["weights"]).is_file()
     assert best["Val/Loss"] == min(recs[1]["Val/Loss"], recs[1]["Val EMA/Loss"])
-    _child(["--convert", "true", "--use-best", f"--log_dir={log}"] + cli_runs["common"])
+    child("train", ["--convert", "true", "--use-best", f"--log_dir={log}"] + cli_runs["common"])
     wav = log / "generation" / "spk000_to_spk001" / "convert_spk000_to_spk001_utt000.wav"
     assert wav.is_file() and wav.stat().st_size > 44
 
 
 def test_resume_with_another_split_exits(cli_runs):
-    r = _child(["--train", "true", f"--log_dir={cli_runs['val']}", "--val-fraction", "0.4", "--ema-decay", "0.9"]
+    r = child("train", ["--train", "true", f"--log_dir={cli_runs['val']}", "--val-fraction", "0.4", "--ema-decay", "0.9"]
                + cli_runs["common"], ok=False)
     assert r.returncode != 0 and "val_split.json" in r.stderr and "val_fraction" in r.stderr and "leak" in r.stderr, \
         (r.returncode, r.stderr[-2000:])
@@ -515,5 +460,5 @@ def test_run_without_the_flags_is_what_it_was(cli_runs):
     assert not {"val_split.json", "val.json"} & set(os.listdir(log))
     assert sorted(os.listdir(log / "checkpoints")) == ["DisentangledVAE_VCTK_2.opt", "DisentangledVAE_VCTK_2.pth"]
     assert not any(k.startswith("val") or k == "use_best" for k in json.load(open(log / "config.json")))
-    r = _child(["--convert", "true", "--use-best", f"--log_dir={log}"] + cli_runs["common"], ok=False)
+    r = child("train", ["--convert", "true", "--use-best", f"--log_dir={log}"] + cli_runs["common"], ok=False)
     assert r.returncode != 0 and "best.json" in r.stderr

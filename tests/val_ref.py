@@ -30,9 +30,8 @@ group_sum_f64: pure float64 additions in row order starting from what the buffer
 """
 import numpy as np
 
-from elem_ref import EPS32, EXPF_ROUNDINGS, g
+from elem_ref import EPS32, EPS64, EXPF_ROUNDINGS, FLOOR, g
 
-EPS64, FLOOR = 2.0 ** -53, 2.0 ** -126
 X = EXPF_ROUNDINGS
 F64, F32 = np.float64, np.float32
 TERMS = ("LOSS", "L1_1", "L1_2", "L1_1hat", "L1_2hat", "KL_1", "KL_2", "KL_style")
