@@ -61,7 +61,7 @@ COMPUTE_MODES = {"fp32": MODE_F32, "f32": MODE_F32, "float32": MODE_F32, "bf16":
                  "fp32x3": MODE_F32X3, "f32x3": MODE_F32X3}
 
 DEFAULT_COMPUTE_DTYPE = "fp32x3"
-ABI_VERSION = 315     # DVAE_ABI_VERSION of include/dvae_hip.h
+ABI_VERSION = 316    # DVAE_ABI_VERSION of include/dvae_hip.h
 
 # name -> (restype, argtypes); mirrors include/dvae_hip.h one to one
 SIGNATURES = {
@@ -138,6 +138,9 @@ SIGNATURES = {
     "dvae_chunks_to_mel": (i32, [vp, vp, i32, i32, i32, f32, f32, i32, vp]),
     "dvae_conversion_latents": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "dvae_mul_div": (i32, [vp, vp, vp, vp, i64, vp]),
+    "dvae_mel_to_windows": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
+    "dvae_window_latents": (i32, [vp, vp, vp, vp, vp, C.c_double, vp, i32, i32, i32, i32, vp]),
+    "dvae_windows_overlap_add": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, f32, i32, vp]),
     "dvae_set_compute_mode": (i32, [i32]),
     "dvae_get_compute_mode": (i32, []),
     "dvae_set_deterministic": (i32, [i32]),

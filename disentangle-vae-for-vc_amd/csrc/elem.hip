@@ -732,6 +732,99 @@ __global__ void conversion_latents_kernel(const float* __restrict__ ss, const fl
     zc[idx] = v;
   }
 }
+// ---- whole-utterance conversion: overlapped windows of a packed batch of utterances
+// utt[u] = {col0, L, win0, nwin}, win[w] = {utt, frame0} (utt < 0: a padding window); mels [C, ld], utterance u in columns
+// [col0, col0 + L).  out[w][c][j] = mels[c][col0 + frame0 + j] while frame0 + j < L, else 0: bits moved, never computed with.
+__global__ __launch_bounds__(256) void mel_to_windows_kernel(const float* __restrict__ mels, int64_t ld,
+                                                             const int* __restrict__ utt, const int* __restrict__ win,
+                                                             float* __restrict__ out, int nwin, int C, int T) {
+  const int64_t total = (int64_t)nwin * C * T;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int j = (int)(i % T);
+    const int c = (int)((i / T) % C);
+    const int w = (int)(i / ((int64_t)T * C));
+    const int u = win[2 * w];
+    float v = 0.f;
+    if (u >= 0) {
+      const int f = win[2 * w + 1] + j;
+      if (f < utt[4 * u + 1]) v = mels[(int64_t)c * ld + utt[4 * u] + f];
+    }
+    out[i] = v;
+  }
+}
+// z[w] = [fp32((1 - mix) mean_src + mix mean_trg) | content_mu[w]] with mean_g = sums[g][:S] / counts[g] in float64 (the sums
+// and counts of dvae_group_sum_f64 over the style heads, K columns a row); a padding window (a group < 0) is a row of zeros.
+__global__ __launch_bounds__(256) void window_latents_kernel(const float* __restrict__ content,
+                                                             const double* __restrict__ sums,
+                                                             const int64_t* __restrict__ counts,
+                                                             const int* __restrict__ g_src, const int* __restrict__ g_trg,
+                                                             double mix, float* __restrict__ z, int nwin, int S, int Cn,
+                                                             int K) {
+  const int D = S + Cn;
+  const int64_t total = (int64_t)nwin * D;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int w = (int)(i / D), d = (int)(i % D);
+    const int gs = g_src[w], gt = g_trg[w];
+    float v = 0.f;
+    if (gs >= 0 && gt >= 0) {
+      if (d < S) {
+        const double a = sums[(int64_t)gs * K + d] / (double)counts[gs];
+        const double b = sums[(int64_t)gt * K + d] / (double)counts[gt];
+        v = (float)((1.0 - mix) * a + mix * b);
+      } else {
+        v = content[(int64_t)w * 2 * Cn + (d - S)];
+      }
+    }
+    z[i] = v;
+  }
+}
+// The gather form of the cross-fade: one thread per element (c, q) of out [C, ld].  Column q belongs to the utterance u with
+// col0 <= q < col0 + L (col0 increases with u: a bisection), t = q - col0; the windows of u are contiguous and their frame0
+// increases, so those that cover t are a run that starts at the first one with frame0 > t - T (a second bisection).  One
+// window in the run: its value's bits.  More: num = sum w[t - frame0] y, den = sum w[t - frame0] in float64 in window order,
+// out = fp32(num / den).  A column that no utterance owns is not written.
+__global__ __launch_bounds__(256) void windows_overlap_add_kernel(const float* __restrict__ y, const int* __restrict__ utt,
+                                                                  const int* __restrict__ win, const float* __restrict__ wt,
+                                                                  float* __restrict__ out, int64_t ld, int nutt, int C,
+                                                                  int T, float lo, float hi, int clamp) {
+  const int64_t total = (int64_t)C * ld;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i / ld);
+    const int64_t q = i % ld;
+    int a = 0, b = nutt;                       // the last utterance with col0 <= q
+    while (b - a > 1) {
+      const int m = (a + b) >> 1;
+      if (utt[4 * m] <= q) a = m; else b = m;
+    }
+    const int col0 = utt[4 * a], L = utt[4 * a + 1], win0 = utt[4 * a + 2], nw = utt[4 * a + 3];
+    if (q < col0 || q >= (int64_t)col0 + L || nw < 1) continue;
+    const int t = (int)(q - col0);
+    int p = 0, e = nw;                         // the first window with frame0 > t - T
+    while (p < e) {
+      const int m = (p + e) >> 1;
+      if (win[2 * (win0 + m) + 1] > t - T) e = m; else p = m + 1;
+    }
+    if (p >= nw || win[2 * (win0 + p) + 1] > t) continue;      // a frame no window covers: a broken plan, left unwritten
+    const float* yc = y + (int64_t)c * T;
+    const int64_t wstride = (int64_t)C * T;
+    float v;
+    if (p + 1 >= nw || win[2 * (win0 + p + 1) + 1] > t) {
+      v = yc[(win0 + p) * wstride + (t - win[2 * (win0 + p) + 1])];
+    } else {
+      double num = 0.0, den = 0.0;
+      for (int k = p; k < nw; ++k) {
+        const int j = t - win[2 * (win0 + k) + 1];
+        if (j < 0) break;
+        const double wj = (double)wt[j];
+        num += wj * (double)yc[(win0 + k) * wstride + j];
+        den += wj;
+      }
+      v = (float)(num / den);
+    }
+    if (clamp) v = fminf(fmaxf(v, lo), hi);
+    out[i] = v;
+  }
+}
 __global__ __launch_bounds__(256) void mul_div_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                       const float* __restrict__ c, float* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
@@ -1044,6 +1137,29 @@ DVAE_API int dvae_conversion_latents(const float* src_style, const float* src_co
   const int total = n * (S + Cn);
   hipLaunchKernelGGL(conversion_latents_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, src_style,
                      src_content, trg_style, z_src, z_conv, n, m, S, Cn);
+  return dvae_check_launch();
+}
+DVAE_API int dvae_mel_to_windows(const float* mels, int64_t ld, const int* utt_table, const int* win_table, float* out,
+                                 int nwin, int C, int T, void* stream) {
+  if (!mels || !utt_table || !win_table || !out || ld < 1 || nwin < 1 || C < 1 || T < 1) return DVAE_EINVAL;
+  hipLaunchKernelGGL(mel_to_windows_kernel, dim3(nblk((int64_t)nwin * C * T)), dim3(256), 0, (hipStream_t)stream, mels, ld,
+                     utt_table, win_table, out, nwin, C, T);
+  return dvae_check_launch();
+}
+DVAE_API int dvae_window_latents(const float* content, const double* sums, const int64_t* counts, const int* g_src,
+                                 const int* g_trg, double mix, float* z, int nwin, int S, int Cn, int K, void* stream) {
+  if (!content || !sums || !counts || !g_src || !g_trg || !z || nwin < 1 || S < 1 || Cn < 1 || K < S) return DVAE_EINVAL;
+  if (!(mix >= 0.0 && mix <= 1.0)) return DVAE_EINVAL;
+  hipLaunchKernelGGL(window_latents_kernel, dim3(nblk((int64_t)nwin * (S + Cn))), dim3(256), 0, (hipStream_t)stream, content,
+                     sums, counts, g_src, g_trg, mix, z, nwin, S, Cn, K);
+  return dvae_check_launch();
+}
+DVAE_API int dvae_windows_overlap_add(const float* y, const int* utt_table, const int* win_table, const float* w, float* out,
+                                      int64_t ld, int nutt, int C, int T, float lo, float hi, int clamp, void* stream) {
+  if (!y || !utt_table || !win_table || !w || !out || ld < 1 || nutt < 1 || C < 1 || T < 1) return DVAE_EINVAL;
+  if (clamp && !(lo <= hi)) return DVAE_EINVAL;
+  hipLaunchKernelGGL(windows_overlap_add_kernel, dim3(nblk((int64_t)C * ld)), dim3(256), 0, (hipStream_t)stream, y, utt_table,
+                     win_table, w, out, ld, nutt, C, T, lo, hi, clamp);
   return dvae_check_launch();
 }
 DVAE_API int dvae_mul_div(const float* a, const float* b, const float* c, float* out, int64_t n, void* stream) {

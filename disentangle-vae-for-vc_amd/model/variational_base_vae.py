@@ -540,6 +540,18 @@ class VariationalBaseModelVAE:
         finally:
             m.train(was_training)
 
+    @torch.no_grad()
+    def convert_utterances(self, sources, targets, bank=None, style_mix=1.0, recons=False, hop=None, batch=32):
+        """Whole utterances through overlapped, cross-faded windows (convert.Converter.convert):
+        per source a dict with "converted" [80, L], exactly L frames.  Like convert_mel it runs the weights that are in place
+        (inside `with trainer.ema_weights():` the averaged ones) in eval mode and leaves `model.training` as it found it."""
+        from ..convert import Converter
+        was_training = self.model.training
+        try:
+            return Converter(self, hop=hop, batch=batch).convert(sources, targets, bank, style_mix, recons)
+        finally:
+            self.model.train(was_training)
+
     @staticmethod
     def _note_best(checkpoints_path, base, epoch, val):
         """`best.json` names the checkpoint with the lowest Val/Loss seen at any checkpoint so far (an existing file counts:

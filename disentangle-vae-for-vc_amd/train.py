@@ -19,6 +19,9 @@ voiced by the GPU Griffin-Lim inverse of the mel front-end (frontend.MelInverter
 reference's WaveNet, whose code and weights are not part of the reference, and written to
 <log_dir>/generation/<src>_to_<trg>/convert_<src>_to_<trg>_<utt>.wav (16 kHz mono PCM-16) with the source, reconstructed
 and converted mels as .npy.
+--convert --overlap HOP (new, opt-in): the same files through convert.Converter — every source whole, covered by windows HOP
+frames apart and cross-faded on the device, exactly its own frame count, in the mean style of the first --trg-utts sorted
+utterances of --trg_spk (all by default), --style-mix blending it with the source's own; the same file names.
 
 Data parallel (new; the reference is single-device, train.py:49-58): started as one of WORLD_SIZE > 1 ranks —
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 -m dvae_amd.train ...` or with
@@ -93,6 +96,13 @@ def get_parse():
     p.add_argument("--val-interval", type=int, default=1, help="validate every N epochs (and at every checkpoint)")
     p.add_argument("--use-best", action="store_true", default=False,
                    help="--convert: voice the checkpoint that checkpoints/best.json names (lowest Val/Loss)")
+    p.add_argument("--overlap", type=int, default=0,
+                   help="--convert: whole utterances through windows HOP frames apart, cross-faded (convert.Converter), with the "
+                        "mean style of the target speaker's utterances (0: the reference's disjoint chunks)")
+    p.add_argument("--trg-utts", type=int, default=0,
+                   help="--convert --overlap: the style comes from the first N sorted utterances of --trg_spk (0: all)")
+    p.add_argument("--style-mix", type=float, default=1.0,
+                   help="--convert --overlap: 1 the target's style, 0 the source's own mean style, between: a blend")
     return p
 
 
@@ -267,6 +277,8 @@ def convert(vsc, args, logging_func=print):
     targets = sorted(glob(os.path.join(args.dataset_fp, trg, "*.npy")))
     if not sources or not targets:
         raise SystemExit(f"--convert: no .npy utterances under {args.dataset_fp}/{src} or {args.dataset_fp}/{trg}")
+    if getattr(args, "overlap", 0):
+        return convert_overlapped(vsc, args, sources, targets, save_dir, logging_func)
     rng = np.random.RandomState(args.seed)
     names, converted = [], []
     for fp in sources:
@@ -283,6 +295,43 @@ def convert(vsc, args, logging_func=print):
     gen = torch.Generator(device=vsc.device)
     gen.manual_seed(args.seed)
     wavs = inv.waveform_batch(converted, n_iter=args.griffin_lim_iters, generator=gen)
+    for name, w in zip(names, wavs):
+        write_wav(os.path.join(save_dir, name), w.cpu().numpy(), inv.sr)
+        logging_func(f"wrote {os.path.join(save_dir, name)}")
+    return [os.path.join(save_dir, n) for n in names]
+
+
+def convert_overlapped(vsc, args, sources, targets, save_dir, logging_func=print):
+    """--convert --overlap HOP: the corpus files through convert.Converter — every source whole, exactly its own frame count,
+    in the mean style of the first --trg-utts target utterances; file names as the chunk path writes them."""
+    import numpy as np
+
+    from .convert import Converter
+    from .frontend import MelInverter
+    src, trg = args.src_spk, args.trg_spk
+    if not 0.0 <= args.style_mix <= 1.0:
+        raise SystemExit(f"--style-mix {args.style_mix}: a weight in [0, 1]")
+    try:
+        conv = Converter(vsc, hop=args.overlap, batch=32)
+    except ValueError as e:
+        raise SystemExit(f"--overlap: {e}")
+    if args.trg_utts > 0:
+        targets = targets[:args.trg_utts]
+    bank = conv.style_bank({trg: [np.load(t) for t in targets]})
+    mels = [np.load(fp) for fp in sources]
+    res = conv.convert(mels, trg, bank, style_mix=args.style_mix, recons=True)
+    names = []
+    for fp, mel, r in zip(sources, mels, res):
+        utt = utterance_id(fp)
+        logging_func(f"convert utterance: {utt} from --->{src} to --->{trg} ({len(targets)} target utterances, hop {conv.hop})")
+        np.save(os.path.join(save_dir, f"source_{src}_{utt}.npy"), np.asarray(mel, dtype=np.float32))
+        np.save(os.path.join(save_dir, f"recons_{src}_{utt}.npy"), r["recons"].cpu().numpy())
+        np.save(os.path.join(save_dir, f"convert_{src}_to_{trg}_{utt}.npy"), r["converted"].cpu().numpy())
+        names.append(f"convert_{src}_to_{trg}_{utt}.wav")
+    inv = MelInverter(device=vsc.device)
+    gen = torch.Generator(device=vsc.device)
+    gen.manual_seed(args.seed)
+    wavs = inv.waveform_batch([r["converted"] for r in res], n_iter=args.griffin_lim_iters, generator=gen)
     for name, w in zip(names, wavs):
         write_wav(os.path.join(save_dir, name), w.cpu().numpy(), inv.sr)
         logging_func(f"wrote {os.path.join(save_dir, name)}")
@@ -319,6 +368,10 @@ def main(argv=None):
         val_keys = ("val_fraction", "val_speakers", "val_seed", "val_interval", "use_best")
         if all(cfg[k] == get_parse().get_default(k) for k in val_keys):
             for k in val_keys:      # none of the validation flags given: the file a run wrote before they existed
+                del cfg[k]
+        conv_keys = ("overlap", "trg_utts", "style_mix")
+        if all(cfg[k] == get_parse().get_default(k) for k in conv_keys):
+            for k in conv_keys:     # likewise the flags of the overlapped conversion
                 del cfg[k]
         with open(os.path.join(args.log_dir, "config.json"), "w") as fp:
             json.dump(cfg, fp, indent=4)

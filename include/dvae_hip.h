@@ -44,7 +44,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 315
+#define DVAE_ABI_VERSION 316
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -494,6 +494,32 @@ int dvae_chunks_to_mel(const float* in, float* out, int n, int C, int T, float l
 int dvae_conversion_latents(const float* src_style, const float* src_content, const float* trg_style,
                             float* z_src, float* z_conv, int n, int m, int S, int Cn, void* stream);
 int dvae_mul_div(const float* a, const float* b, const float* c, float* out, int64_t n, void* stream);
+
+/* ---- inference: whole utterances through overlapped windows (in place of chunking_mel, variational_base_vae.py:335-348, and
+ * of the per-chunk latents and torch.cat of voice_conversion_mel, :269-298, which join nothing at a chunk border).
+ * A batch of utterances lies packed in mels [C, ld]: utterance u owns columns [col0, col0 + L).  Two int32 device tables:
+ *   utt_table[nutt][4] = {col0, L, win0, nwin}   col0 increasing with u; windows win0 ... win0 + nwin - 1 are u's
+ *   win_table[nwin][2] = {utt, frame0}           frame0 increasing inside an utterance; utt < 0: a padding window
+ * (dvae_amd.convert.flat_plan writes them).
+ * dvae_mel_to_windows: out[w][c][j] = mels[c][col0 + frame0 + j] while frame0 + j < L, else 0; a padding window is all zeros.
+ *   A pure copy: columns that no utterance owns are never read.
+ * dvae_window_latents: sums [G][K] float64 and counts [G] int64 as dvae_group_sum_f64 leaves them for the style heads (K = 2 S,
+ *   the first S columns style_mu).  z[w][:S] = fp32((1 - mix) sums[g_src[w]] / counts[g_src[w]] + mix sums[g_trg[w]] /
+ *   counts[g_trg[w]]) in float64, rounded once (the compiler may fuse the last multiply and add); z[w][S:] = content[w][:Cn],
+ *   bits copied (content [nwin][2 Cn] = mu | logvar).  mix = 1: conversion, mix = 0: the source's own mean style, 0 <= mix <= 1.
+ *   A window with g_src < 0 or g_trg < 0 is a row of zeros.  counts live on the device: the caller makes sure that no group
+ *   in use is empty (dvae_amd.convert refuses it before the launch).
+ * dvae_windows_overlap_add: out[c][col0 + t], t < L, from y [nwin][C][T]: where ONE window covers frame t its value's bits;
+ *   elsewhere num = sum w[t - frame0] y[win][c][t - frame0], den = sum w[t - frame0] over the covering windows in window
+ *   order, float64, out = fp32(num / den); then the optional clamp to [lo, hi] (:296).  One thread per output element, no
+ *   atomics: two launches give the same bits.  Columns that no utterance owns are not written.  w [T] fp32, positive.
+ * Null pointers, sizes < 1, a mix outside [0, 1] or lo > hi return DVAE_EINVAL and launch nothing. */
+int dvae_mel_to_windows(const float* mels, int64_t ld, const int* utt_table, const int* win_table, float* out, int nwin,
+                        int C, int T, void* stream);
+int dvae_window_latents(const float* content, const double* sums, const int64_t* counts, const int* g_src, const int* g_trg,
+                        double mix, float* z, int nwin, int S, int Cn, int K, void* stream);
+int dvae_windows_overlap_add(const float* y, const int* utt_table, const int* win_table, const float* w, float* out,
+                             int64_t ld, int nutt, int C, int T, float lo, float hi, int clamp, void* stream);
 
 /* ---- mel front-end: preprocessing/utils.py:68-73 `melspectrogram` = lws STFT (1024/256, "speech" window)
  * -> |.| -> 80-mel projection (librosa.filters.mel) -> dB (:127-129) - ref_level_db -> normalise to [0,1] (:136-137).
