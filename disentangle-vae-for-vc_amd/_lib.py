@@ -61,7 +61,7 @@ COMPUTE_MODES = {"fp32": MODE_F32, "f32": MODE_F32, "float32": MODE_F32, "bf16":
                  "fp32x3": MODE_F32X3, "f32x3": MODE_F32X3}
 
 DEFAULT_COMPUTE_DTYPE = "fp32x3"
-ABI_VERSION = 316    # DVAE_ABI_VERSION of include/dvae_hip.h
+ABI_VERSION = 317    # DVAE_ABI_VERSION of include/dvae_hip.h
 
 # name -> (restype, argtypes); mirrors include/dvae_hip.h one to one
 SIGNATURES = {
@@ -167,6 +167,9 @@ SIGNATURES = {
     "dvae_dtw_batch_f0": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "dvae_softmax_ce": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, vp]),
     "dvae_scale_by": (i32, [vp, vp, vp, i64, vp]),
+    "dvae_gmm_ws_bytes": (C.c_size_t, [i64, i32, i32]),
+    "dvae_gmm_estep": (i32, [vp, i64, i32, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+    "dvae_gmm_score": (i32, [vp, i64, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp]),
     "dvae_pair_metrics": (i32, [vp] * 9 + [i32, i64, i32, i32, f32, f32, vp]),
     "dvae_group_sum_f64": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "dvae_prof_enable": (i32, [i32]),

@@ -24,6 +24,7 @@
 #ifndef DVAE_HIP_H
 #define DVAE_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -44,7 +45,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 316
+#define DVAE_ABI_VERSION 317
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -674,6 +675,39 @@ int dvae_dtw_batch_f0(const float* x, const float* y, const float* lf0x, const f
 int dvae_softmax_ce(const float* logits, const int* labels, float* dlogits, float* row_loss, int* row_pred, float* out,
                     int rows, int classes, int64_t ld, float grad_scale, void* stream);
 int dvae_scale_by(const float* x, const float* scale, float* y, int64_t n, void* stream);
+
+/* ---- GMM-UBM speaker verification of conversions (python -m dvae_amd.verify) ----
+ * Replaces nothing of the reference (it has no speaker-verification score): Reynolds, Quatieri, Dunn (2000) on the
+ * mel-cepstra of dvae_voicing_compact.  A diagonal-covariance mixture of K components over D dimensions is THREE fp32
+ * tables, computed by the caller in float64 from (w, mu, var) and rounded once (the tables as rounded are the model):
+ *   a[k] = ln w_k - 1/2 sum_d ln(2 pi var_kd),  mu[k][d],  prec[k][d] = 1 / var_kd.
+ * Frame t is x[t * ldx + col0 + d], d < D: ldx >= col0 + D, nothing assumed of x beyond 4-byte alignment (feats
+ * [rows, 24] is read in place with col0 = 1, D = 23).  Per frame, in fp32, the same device function in both entry points:
+ *   l_kt  = a_k - 1/2 sum_d (x_td - mu_kd)^2 prec_kd      (d ascending, one fma per term)
+ *   lse_t = m_t + ln sum_k exp(l_kt - m_t), m_t = max_k l_kt   (k ascending; finite however far the frame is)
+ * dvae_gmm_estep: lse [N] and gamma [N, K] (gamma_tk = exp(l_kt - lse_t), fp32, formed as exp(l_kt - m_t) over the sum so
+ *   that a row adds up to 1 within K 2^-23 however large |lse_t| is) are optional (null: not written);
+ *   stats, K (1 + 2 D) + 1 doubles, is OVERWRITTEN: per component k the record {n_k = sum_t gamma_tk, f_kd = sum_t gamma_tk
+ *   x_td (d < D), s_kd = sum_t gamma_tk x_td^2 (d < D)} at stats[k (1 + 2 D)], and sum_t lse_t in the last double.  Every
+ *   term is formed in float64 from the fp32 gamma and x and every sum is float64 in a fixed order: a workgroup owns
+ *   consecutive tiles of 256 / 128 / 64 frames (K <= 64 / <= 128 / above) and one thread per output walks their frames in
+ *   order; the partition is a function of (N, K, D) alone; per-workgroup sums go to ws (dvae_gmm_ws_bytes(N, K, D) bytes,
+ *   nothing behind them is touched) and a second launch adds them in index order.  No atomics: two calls, or a call
+ *   without lse / gamma, give the same bits.  ws and stats 8-byte aligned.
+ * dvae_gmm_score: segs [nseg][2] int64 {row0, count} marks contiguous rows of x; M <= 65535 models lie back to back
+ *   (a [M][K], mu [M][K][D], prec [M][K][D]); out[s][m] = sum of lse_t under model m over segment s, float64, exactly
+ *   0.0 for count = 0.  One workgroup per (segment, model): thread i adds frames i, i + 256, ... in that order, then the
+ *   xor tree over the 64 lanes of a wave (offsets 32 .. 1) and the four waves in order, so a row of out has the same bits
+ *   whatever else is in the batch and equals that sum of dvae_gmm_estep's own lse.  segs and out 8-byte aligned.
+ * Null required pointers, N, K, D, M, nseg < 1, K > DVAE_GMM_MAX_K, D > DVAE_GMM_MAX_DIM, col0 < 0, ldx < col0 + D or a
+ *   misaligned float64 / int64 buffer return DVAE_EINVAL and launch nothing (dvae_gmm_ws_bytes returns 0). */
+#define DVAE_GMM_MAX_K 256
+#define DVAE_GMM_MAX_DIM 32
+size_t dvae_gmm_ws_bytes(int64_t N, int K, int D);
+int dvae_gmm_estep(const float* x, int64_t ldx, int col0, int64_t N, int D, const float* a, const float* mu,
+                   const float* prec, int K, float* lse, float* gamma, void* ws, double* stats, void* stream);
+int dvae_gmm_score(const float* x, int64_t ldx, int col0, int D, const int64_t* segs, int nseg, const float* a,
+                   const float* mu, const float* prec, int K, int M, double* out, void* stream);
 
 /* ---- held-out validation (model/variational_base_vae.py: validate) ----
  * The reference's test() (variational_base_vae.py:105-123) sums loss_functionGVAE2 (disentangled_vae.py:310-327) over the
