@@ -315,8 +315,9 @@ class DisentangledVAE(nn.Module):
         Returns (h, h16) the same way: h16 is None unless the layer keeps its state in bf16 (then h is the placeholder)."""
         mod = getattr(self, mname)
         from ..derived import lstm_pack_modes
-        # both passes on the W_hh-resident launches (bf16 mode): two plain layers; otherwise (fp32x3: forward only — inside
-        # LstmStack2Fn — or none) two stacked layers of equal width share their per-frame launches
+        # both passes on the W_hh-resident launches or neither (lstm_persistent_usable answers per pass, in every compute
+        # mode): persistent — plain layers, one launch per layer and pass; not — two stacked layers of equal width share
+        # their per-frame launches, any other layer runs per frame on its own
         mf, mb = lstm_pack_modes(ops.current_mode(), mod.hidden_size)
         ndir = 2 if mod.bidirectional else 1
         pers = ops.lstm_persistent_usable(n_seg, mod.hidden_size, mf, ndir) and \

@@ -172,11 +172,16 @@ SLAB_CAP = 16                # slabs provided to a split contraction = the most 
                              # further themselves, to one workgroup per CU)
 
 
+def _dev_index(dev) -> int:
+    """Index of the GPU that `dev` ("cuda", "cuda:1", a torch.device) names: the current device when it names none."""
+    idx = torch.device(dev).index
+    return idx if idx is not None else torch.cuda.current_device()
+
+
 def _stream_key(dev):
     """One scratch / workspace per device for the launches of the caller's stream (a captured graph replays on it and uses the
     buffers the eager first step created), a second one for the opt-in side stream (its launches run beside the main stream's)."""
-    d = torch.device(dev)
-    idx = d.index if d.index is not None else torch.cuda.current_device()
+    idx = _dev_index(dev)
     side = _side_stream is not None and torch.cuda.current_stream(idx).cuda_stream == _side_stream.cuda_stream
     return idx, bool(side)
 
@@ -841,7 +846,7 @@ def lstm_pers_workspace(dev) -> torch.Tensor:
     (One exchange slot PER FRAME read with plain, L2-cached loads was tried and removed: wrong results under hipGraph
     replay — blamed on stale L2 lines then, possibly the flag-clear hazard of the memset node that was in use — and no
     faster; DESIGN_HISTORY.md.)"""
-    key = torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device()
+    key = _dev_index(dev)
     ws = _pers_ws.get(key)
     if ws is None:
         ws = _pers_ws[key] = torch.zeros(_PERS_WS_BYTES, device=f"cuda:{key}", dtype=torch.uint8)
@@ -866,7 +871,7 @@ def _pers_claim(dev):
     is exempt (torch synchronises the device around a capture; a replayed graph runs on the stream that replays it)."""
     if torch.cuda.is_current_stream_capturing():
         return
-    key = torch.device(dev).index if torch.device(dev).index is not None else torch.cuda.current_device()
+    key = _dev_index(dev)
     cur = torch.cuda.current_stream(key)
     own = _pers_owner.get(key)
     if own is not None and own.cuda_stream != cur.cuda_stream and not own.query():
@@ -876,18 +881,19 @@ def _pers_claim(dev):
     _pers_owner[key] = cur
 
 
-def _pers_fill(d, dev):
-    """pers_ws / pers_timeout_us of a dvae_lstm_dir_t"""
+def _pers_fill(d, dev, dbias_part=None):
+    """What only a persistent launch reads of a dvae_lstm_dir_t (after _lstm_dir, which clears it): pers_ws / pers_timeout_us
+    and, backward, the bias-gradient slabs (pers_bias_slabs)."""
     _pers_claim(dev)
-    d.pers_ws, d.pers_timeout_us = ptr(lstm_pers_workspace(dev)), LSTM_PERS_TIMEOUT_US
+    d.pers_ws, d.pers_timeout_us, d.dbias_part = ptr(lstm_pers_workspace(dev)), LSTM_PERS_TIMEOUT_US, ptr(dbias_part)
 
 
 def lstm_pers_check():
     """Synchronises the current stream of every device that ran a persistent LSTM launch and raises if a bounded
     cross-workgroup wait gave up (the launch's outputs are garbage then).  Call where the host synchronises anyway."""
-    for key, ws in _pers_ws.items():
+    for ws in _pers_ws.values():
         info = (C.c_int * 4)()
-        with torch.cuda.device(key):
+        with torch.cuda.device(_dev_index(ws.device)):
             rc = lib().dvae_lstm_pers_check(ptr(ws), info, stream())
         if rc != 0:
             raise _lib.DvaeHipError(f"persistent LSTM launch gave up a bounded wait: pass {info[0]} (1 fwd, 2 bwd), "
@@ -926,6 +932,69 @@ def pers_bias_fold(bi, bh, part: torch.Tensor, H: int):
         _defer_fold(par.grad, _owner_of(par), part.data_ptr(), 4 * H, _lib.PERS_BIAS_SLABS, n=4 * H)
 
 
+def _addr(t, off=0):
+    """Address `off` bytes into a tensor (an integer is an address already); None stays NULL."""
+    return None if t is None else (t if isinstance(t, int) else t.data_ptr()) + off
+
+
+def _lstm_dir(e, *, H, gates, w_hh, w_packed, packed_mode, c_all, state_bf16, d=0, gate_ld=0, reverse=0, step_shift=0,
+              h_out=None, dh_out=None, dgates=None, dc_ws=None):
+    """Writes EVERY field of the dvae_lstm_dir_t `e`: the one place with the byte offsets of a launch descriptor.  Pure — it
+    reads data_ptr() (or takes integer addresses), allocates and launches nothing; _pers_fill adds a persistent launch's part.
+    `d`: the direction's column block in the state tensors of its layer, h_out (bf16 with `state_bf16`) and dh_out (always
+    fp32), both [R, ndir*H] and given whole; 0 where a layer owns them (one direction, each layer of a stacked pair).
+    `gate_ld`: row stride of gates (fp32) and dgates (bf16 with `state_bf16`), 0 = 4H; with 8H (H = 64: both directions side
+    by side) they are given as the shared [R, 8H] tensors and the entry starts at column d*4H.
+    Forward: w_hh [4H, H], the forward pack, h_out.  Backward: w_hh = W_hh^T, the backward pack, dh_out, dgates, dc_ws."""
+    esz = 2 if state_bf16 else 4
+    gcol = d * 4 * H if gate_ld == 8 * H else 0
+    e.gates, e.dgates, e.gate_ld = _addr(gates, 4 * gcol), _addr(dgates, esz * gcol), gate_ld
+    e.h_out, e.dh_out = _addr(h_out, esz * d * H), _addr(dh_out, 4 * d * H)
+    e.w_hh, e.w_packed, e.packed_mode, e.c_all, e.dc_ws = _addr(w_hh), _addr(w_packed), packed_mode, _addr(c_all), _addr(dc_ws)
+    e.reverse, e.step_shift, e.state_bf16 = reverse, step_shift, int(state_bf16)
+    e.pers_ws, e.pers_timeout_us, e.dbias_ih, e.dbias_hh, e.dbias_part = None, 0, None, None, None
+
+
+def _lstm_in_proj(x, wi, der, g, rows, H, In, mode, flags=0):
+    """Input projection of one direction: g[rows, 4H] = x[rows, In] W_ih^T + (b_ih + b_hh); x, g: tensors or addresses."""
+    gemm(x, wi if der.w_ih16 is None else der.w_ih16, g, der.bias, rows, 4 * H, In, In, In, 4 * H, True, True, mode=mode,
+         flags=flags)
+
+
+def _lstm_hprev(dg, h, d, N, H, ldg, ldh, esz, reverse):
+    """Operand addresses of a W_hh gradient over the (T-1)*N rows that have an h_prev — h[t-1] (forward) / h[t+1] (reverse):
+    dg (the direction's dgates, row stride ldg) against h (the layer's state, row stride ldh, the direction at column d*H)."""
+    return (_addr(dg), _addr(h, esz * (N * ldh + d * H))) if reverse else (_addr(dg, esz * N * ldg), _addr(h, esz * d * H))
+
+
+def _lstm_wgrad(dg, inp, h, d, ldh, params, T, N, H, reverse, s16, mode, bias_done):
+    """The gradients of one direction of one layer from its dgates `dg` [T*N, 4H], the single place for that tail: W_ih from
+    the layer input, W_hh from the state `h` a frame away, both biases unless the persistent launch left them (`bias_done`)."""
+    wi, wh, bi, bh = params
+    linear_wgrad_acc(dg, inp, _grad_buf(wi), mode=mode, owner=_owner_of(wi))
+    gw = _grad_buf(wh)      # exists (zero) even when T == 1 leaves W_hh without a gradient
+    if T > 1:
+        rows = (T - 1) * N
+        a_ptr, b_ptr = _lstm_hprev(dg, h, d, N, H, 4 * H, ldh, 2 if s16 else 4, reverse)
+        sk = _split_k(_tiles(4 * H, H), rows)
+        wgrad_gemm(a_ptr, b_ptr, gw, _owner_of(wh), 4 * H, H, rows, 4 * H, ldh, False, False, sk, mode,
+                   flags=(A_BF16 | B_BF16) if s16 else 0)
+    if not bias_done:
+        colsum_add(dg, _grad_buf(bi), _grad_buf(bh))
+
+
+def _lstm_return(ctx, h, s16, emit16):
+    """What an LSTM forward returns for its state `h` (emit16: see LstmLayerFn.forward); bf16 state without emit16 — stand-alone
+    use in the bf16 mode — comes back as a real fp32 copy."""
+    if not s16:
+        return (h, None) if emit16 else h
+    if emit16:
+        ctx.mark_non_differentiable(h)
+        ctx.set_materialize_grads(False)
+        return _placeholder(h.shape[0], h.shape[1], h.device), h
+    return h.float()
+
+
 class LstmLayerFn(torch.autograd.Function):
     """One nn.LSTM layer (1 or 2 directions) over frame-major rows: x[T*N, In] -> h[T*N, ndir*H].
     Reference: enc_lstm :163/:208, dec_lstm1 :172/:238, dec_lstm2 :193/:246.
@@ -937,23 +1006,19 @@ class LstmLayerFn(torch.autograd.Function):
         (bf16), h its fp32 placeholder for autograd (see ConvBnActFn); otherwise h is a real fp32 tensor and h16 None."""
         x = x if x16 is None else x16                     # bf16 mode: the DATA of a placeholder input
         _ok(x, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r, act16=(x,))
-        L = lib()
-        st = stream()
-        dev = x.device
+        L, st, dev = lib(), stream(), x.device
         R, In = x.shape
         H = w_hh.shape[1]
         ndir = 2 if w_ih_r is not None else 1
         ldh = ndir * H
-        mode0 = current_mode()
-        s16 = mode0 == MODE_BF16 and H % 512 == 0         # bf16 state / gate-gradient storage (frame kernels with S16)
+        mode = current_mode()
+        s16 = mode == MODE_BF16 and H % 512 == 0          # bf16 state / gate-gradient storage (frame kernels with S16)
         h_out = torch.empty((R, ldh), device=dev, dtype=torch.bfloat16 if s16 else torch.float32)
-        esz = h_out.element_size()
         params = [(w_ih, w_hh, b_ih, b_hh), (w_ih_r, w_hh_r, b_ih_r, b_hh_r)][:ndir]
         dirs = (_lib.LstmDir * ndir)()
         # bf16 / fp32x3 compute modes: the recurrence runs on bf16 fragments (one plane / three planes) where such frame
         # kernels exist (H = 512, 1024); the H = 64 encoder recurrence (3 % of the FLOPs, weights resident in registers)
         # stays on the fp32 MFMA
-        mode = current_mode()
         from .derived import lstm_pack_modes
         bf, bfb = lstm_pack_modes(mode, H)      # (forward, backward) precision of the recurrent product
         der = _lstm_derived(derived, params, mode)
@@ -969,35 +1034,18 @@ class LstmLayerFn(torch.autograd.Function):
                 g = gall[:, d * 4 * H:(d + 1) * 4 * H]
             else:
                 g = torch.empty((R, 4 * H), device=dev, dtype=torch.float32)
-                gemm(x, wi if der[d].w_ih16 is None else der[d].w_ih16, g, der[d].bias, R, 4 * H, In, In, In, 4 * H, True,
-                     True, mode=mode)
+                _lstm_in_proj(x, wi, der[d], g, R, H, In, mode)
             c = torch.empty((R, H), device=dev, dtype=torch.float32)
             gates.append(g)
             cells.append(c)
-            dirs[d].gate_ld = ldg
-            dirs[d].gates = ptr(g)
-            dirs[d].w_hh = ptr(wh)
-            dirs[d].w_packed = ptr(der[d].pack_f)
-            dirs[d].packed_mode = bf
-            dirs[d].h_out = h_out.data_ptr() + esz * d * H
-            dirs[d].c_all = ptr(c)
-            dirs[d].reverse = d
-            dirs[d].state_bf16 = int(s16)
-        pers = lstm_persistent_usable(N, H, bf, ndir)
-        if pers:
+            _lstm_dir(dirs[d], H=H, d=d, gates=g if cat is None else gall, gate_ld=ldg, w_hh=wh, w_packed=der[d].pack_f,
+                      packed_mode=bf, c_all=c, state_bf16=s16, reverse=d, h_out=h_out)
+        if lstm_persistent_usable(N, H, bf, ndir):
             _pers_fill(dirs[0], dev)
         check(L.dvae_lstm_seq_fwd(dirs, ndir, T, N, H, ldh, st), "dvae_lstm_seq_fwd")
         ctx.save_for_backward(x, h_out, *gates, *cells, *[p for ps in params for p in ps])
-        ctx.der = der
-        ctx.cfg = (T, N, H, ndir, bfb, mode, s16)
-        ctx.cat = cat
-        if not s16:
-            return (h_out, None) if emit16 else h_out
-        if emit16:
-            ctx.mark_non_differentiable(h_out)
-            ctx.set_materialize_grads(False)
-            return _placeholder(R, ldh, dev), h_out
-        return h_out.float()          # stand-alone use in the bf16 mode: a real fp32 copy for the caller
+        ctx.der, ctx.cat, ctx.cfg = der, cat, (T, N, H, ndir, bfb, mode, s16)
+        return _lstm_return(ctx, h_out, s16, emit16)
 
     @staticmethod
     def backward(ctx, dh, *_):
@@ -1014,15 +1062,12 @@ class LstmLayerFn(torch.autograd.Function):
         flat = sv[2 + 2 * ndir:]
         params = [flat[4 * d:4 * d + 4] for d in range(ndir)]
         der = ctx.der
-        L = lib()
-        st = stream()
-        dev = x.device
+        L, st, dev = lib(), stream(), x.device
         R, In = x.shape
         ldh = ndir * H
         dh = dh.contiguous()
         dirs = (_lib.LstmDir * ndir)()
-        keep = []
-        dgs = []
+        keep, dgs = [], []
         cat = getattr(ctx, "cat", None)
         ldg = 8 * H if cat is not None else 4 * H
         if cat is not None:        # (H = 64: fp32 gate gradients) both directions side by side, like the gates
@@ -1035,25 +1080,14 @@ class LstmLayerFn(torch.autograd.Function):
             dc = torch.empty((N, H), device=dev, dtype=torch.float32)
             keep.append(dc)
             dgs.append(dg)
-            dirs[d].gate_ld = ldg
-            dirs[d].gates = ptr(gates[d])
-            dirs[d].w_hh = ptr(der[d].w_hh_t)       # [H, 4H]
-            dirs[d].w_packed = ptr(der[d].pack_b)
-            dirs[d].packed_mode = bf
-            dirs[d].c_all = ptr(cells[d])
-            dirs[d].dh_out = dh.data_ptr() + 4 * d * H
-            dirs[d].dgates = ptr(dg)
-            dirs[d].dc_ws = ptr(dc)
-            dirs[d].reverse = d
-            dirs[d].state_bf16 = int(s16)
-        pers = lstm_persistent_usable(N, H, bf, ndir, bwd=True)
-        pers_bias = pers
-        if pers:
-            _pers_fill(dirs[0], dev)
+            _lstm_dir(dirs[d], H=H, d=d, gates=gates[d] if cat is None else gates[0], gate_ld=ldg, w_hh=der[d].w_hh_t,
+                      w_packed=der[d].pack_b, packed_mode=bf, c_all=cells[d], state_bf16=s16, reverse=d, dh_out=dh,
+                      dgates=dg if cat is None else dgall, dc_ws=dc)
+        pers_bias = lstm_persistent_usable(N, H, bf, ndir, bwd=True)
         if pers_bias:
             # the persistent launch also leaves the bias gradients (column sums of dG): no colsum pass below
             part = pers_bias_slabs(params[0][2], params[0][3], H)
-            dirs[0].dbias_part = ptr(part)
+            _pers_fill(dirs[0], dev, part)
         check(L.dvae_lstm_seq_bwd(dirs, ndir, T, N, H, ldh, st), "dvae_lstm_seq_bwd")
         if pers_bias:
             pers_bias_fold(params[0][2], params[0][3], part, H)
@@ -1081,32 +1115,16 @@ class LstmLayerFn(torch.autograd.Function):
                 if T > 1:
                     rows = R - N
                     sk = _split_k(2 * _tiles(4 * H, H), rows)
-                    wgrad_gemm_batched([dgs[0].data_ptr() + esz * N * ldg, dgs[1].data_ptr()],
-                                       [h_out.data_ptr(), h_out.data_ptr() + esz * (N * ldh + H)],
-                                       [params[0][1], params[1][1]], 4 * H, H, rows, ldg, ldh, sk, mode,
-                                       flags=(A_BF16 | B_BF16) if s16 else 0)
+                    ab = [_lstm_hprev(dgs[d], h_out, d, N, H, ldg, ldh, esz, reverse=d) for d in range(2)]
+                    wgrad_gemm_batched([a for a, _ in ab], [b for _, b in ab], [params[0][1], params[1][1]], 4 * H, H, rows,
+                                       ldg, ldh, sk, mode, flags=(A_BF16 | B_BF16) if s16 else 0)
                 else:
                     _grad_buf(params[0][1]), _grad_buf(params[1][1])
-                for d, (wi, wh, bi, bh) in enumerate(params):
-                    if not pers_bias:
-                        colsum_add(dgs[d], _grad_buf(bi), _grad_buf(bh), rows=R, cols=4 * H, ld=ldg)
+                for d, (_, _, bi, bh) in enumerate(params):     # (two directions: never a persistent launch, pers_bias is False)
+                    colsum_add(dgs[d], _grad_buf(bi), _grad_buf(bh), rows=R, cols=4 * H, ld=ldg)
             else:
-              for d, (wi, wh, bi, bh) in enumerate(params):
-                dg = dgs[d]
-                linear_wgrad_acc(dg, x, _grad_buf(wi), mode=mode, owner=_owner_of(wi))
-                gw = _grad_buf(wh)      # exists (zero) even when T == 1 leaves W_hh without a gradient
-                if T > 1:
-                    rows = R - N
-                    # h_prev of frame t is h[t-1] (forward) / h[t+1] (reverse)
-                    if d == 0:
-                        a_ptr, b_ptr = dg.data_ptr() + esz * N * 4 * H, h_out.data_ptr()
-                    else:
-                        a_ptr, b_ptr = dg.data_ptr(), h_out.data_ptr() + esz * (N * ldh + H)
-                    sk = _split_k(_tiles(4 * H, H), rows)
-                    wgrad_gemm(a_ptr, b_ptr, gw, _owner_of(wh), 4 * H, H, rows, 4 * H, ldh, False, False, sk, mode,
-                               flags=(A_BF16 | B_BF16) if s16 else 0)
-                if not pers_bias:
-                    colsum_add(dg, _grad_buf(bi), _grad_buf(bh))
+                for d in range(ndir):
+                    _lstm_wgrad(dgs[d], x, h_out, d, ldh, params[d], T, N, H, d, s16, mode, bias_done=pers_bias)
         for (wi, wh, bi, bh) in params:
             _ready(wi, wh, bi, bh)
         del keep
@@ -1120,6 +1138,9 @@ class LstmStack2Fn(torch.autograd.Function):
     chunk-c outputs went through layer 2's input projection.  Same arithmetic per frame as two LstmLayerFn calls —
     only the launch schedule changes: T + CHUNK launches of 2x the workgroups instead of 2T, two workgroups resident
     per CU so one layer's load latency hides under the other's MFMAs.  Backward mirrors it (layer 2 ahead).
+    The model comes here only where the shape has no persistent launch for BOTH passes (DisentangledVAE._lstm; otherwise two
+    LstmLayerFn).  Called directly where a persistent FORWARD launch exists, forward runs that launch once per layer
+    and backward still the stacked per-frame launches: a branch the model no longer reaches, kept for direct callers.
     `derived`: [LstmDerived of layer 1, LstmDerived of layer 2] (or None)."""
 
     CHUNK = int(os.environ.get("DVAE_LSTM_CHUNK", "-1"))      # frames per chunk; -1: two chunks (T/2), 0: off
@@ -1156,46 +1177,31 @@ class LstmStack2Fn(torch.autograd.Function):
         sdt = dict(device=dev, dtype=torch.bfloat16 if s16 else torch.float32)
         esz = 2 if s16 else 4
         h1, h2 = torch.empty((R, H), **sdt), torch.empty((R, H), **sdt)
-        gemm(x, w_ih1 if der[0].w_ih16 is None else der[0].w_ih16, g1, der[0].bias, R, 4 * H, In, In, In, 4 * H, True, True,
-             mode=mode)
-        dirs = (_lib.LstmDir * 2)()
+        _lstm_in_proj(x, w_ih1, der[0], g1, R, H, In, mode)
+        pers = lstm_persistent_usable(N, H, bf)
+        dirs = (_lib.LstmDir * 2)()     # each layer owns its tensors; stacked launches: layer 2 starts a chunk behind
         for d, (g, wh, h, c) in enumerate(((g1, w_hh1, h1, c1), (g2, w_hh2, h2, c2))):
-            dirs[d].gates, dirs[d].w_hh, dirs[d].w_packed = ptr(g), ptr(wh), ptr(der[d].pack_f)
-            dirs[d].h_out, dirs[d].c_all = ptr(h), ptr(c)
-            dirs[d].reverse, dirs[d].packed_mode, dirs[d].step_shift = 0, bf, (Tc if d == 1 else 0)
-            dirs[d].state_bf16 = int(s16)
-        rows = Tc * N
-        if lstm_persistent_usable(N, H, bf):
-            # the forward recurrences as two W_hh-resident launches (one per layer), layer 2's whole input projection in
-            # between; the backward pass keeps the stacked per-frame launches below
-            one = (_lib.LstmDir * 1)()
-            for d, (g, wh, h, c) in enumerate(((g1, w_hh1, h1, c1), (g2, w_hh2, h2, c2))):
+            _lstm_dir(dirs[d], H=H, gates=g, w_hh=wh, w_packed=der[d].pack_f, packed_mode=bf, c_all=c, state_bf16=s16,
+                      step_shift=Tc if (d == 1 and not pers) else 0, h_out=h)
+        if pers:
+            # the forward recurrences as two W_hh-resident launches (one per layer, each on its own entry), layer 2's whole
+            # input projection in between; the backward pass keeps the stacked per-frame launches below
+            for d in range(2):
                 if d == 1:
-                    gemm(h1, w_ih2 if der[1].w_ih16 is None else der[1].w_ih16, g2, der[1].bias, R, 4 * H, H, H, H, 4 * H,
-                         True, True, mode=mode)
-                one[0].gates, one[0].w_hh, one[0].w_packed = ptr(g), ptr(wh), ptr(der[d].pack_f)
-                one[0].h_out, one[0].c_all = ptr(h), ptr(c)
-                one[0].reverse, one[0].packed_mode, one[0].step_shift, one[0].state_bf16 = 0, bf, 0, int(s16)
-                _pers_fill(one[0], dev)
-                check(L.dvae_lstm_seq_fwd(one, 1, T, N, H, H, st), "dvae_lstm_seq_fwd")
+                    _lstm_in_proj(h1, w_ih2, der[1], g2, R, H, H, mode)
+                _pers_fill(dirs[d], dev)
+                check(L.dvae_lstm_seq_fwd(C.byref(dirs[d]), 1, T, N, H, H, st), "dvae_lstm_seq_fwd")
         else:
+            rows = Tc * N
             for c0 in range(0, T + Tc, Tc):
                 if c0 >= Tc:    # layer 1 finished frames [c0-Tc, c0): their rows go through layer 2's input projection
                     r0 = (c0 - Tc) * N
-                    gemm(h1.data_ptr() + esz * r0 * H, w_ih2 if der[1].w_ih16 is None else der[1].w_ih16,
-                         g2.data_ptr() + 4 * r0 * 4 * H, der[1].bias, rows, 4 * H, H, H, H, 4 * H, True, True, mode=mode,
-                         flags=A_BF16 if s16 else 0)
+                    _lstm_in_proj(h1.data_ptr() + esz * r0 * H, w_ih2, der[1], g2.data_ptr() + 4 * r0 * 4 * H, rows, H, H,
+                                  mode, flags=A_BF16 if s16 else 0)
                 check(L.dvae_lstm_seq_fwd_range(dirs, 2, T, N, H, H, c0, c0 + Tc, st), "dvae_lstm_seq_fwd_range")
         ctx.save_for_backward(x, h1, h2, g1, g2, c1, c2, w_ih1, w_hh1, b_ih1, b_hh1, w_ih2, w_hh2, b_ih2, b_hh2)
-        ctx.der = der
-        ctx.cfg = (T, N, H, bfb, mode, s16)
-        if not s16:
-            return (h2, None) if emit16 else h2
-        if emit16:
-            ctx.mark_non_differentiable(h2)
-            ctx.set_materialize_grads(False)
-            return _placeholder(R, H, dev), h2
-        return h2.float()
+        ctx.der, ctx.cfg = der, (T, N, H, bfb, mode, s16)
+        return _lstm_return(ctx, h2, s16, emit16)
 
     @staticmethod
     def backward(ctx, dh2, *_):
@@ -1215,10 +1221,8 @@ class LstmStack2Fn(torch.autograd.Function):
         # backward step s handles frame T-1-s.  Entry 0 = layer 2 (ahead), entry 1 = layer 1 (a chunk behind).
         dirs = (_lib.LstmDir * 2)()
         for d, (g, dd, c, dho, dg) in enumerate(((g2, der[1], c2, dh2, dg2), (g1, der[0], c1, dh1, dg1))):
-            dirs[d].gates, dirs[d].w_hh, dirs[d].w_packed, dirs[d].c_all = ptr(g), ptr(dd.w_hh_t), ptr(dd.pack_b), ptr(c)
-            dirs[d].dh_out, dirs[d].dgates, dirs[d].dc_ws = ptr(dho), ptr(dg), ptr(dcs[d])
-            dirs[d].reverse, dirs[d].packed_mode, dirs[d].step_shift = 0, bf, (Tc if d == 1 else 0)
-            dirs[d].state_bf16 = int(s16)
+            _lstm_dir(dirs[d], H=H, gates=g, w_hh=dd.w_hh_t, w_packed=dd.pack_b, packed_mode=bf, c_all=c, state_bf16=s16,
+                      step_shift=Tc if d == 1 else 0, dh_out=dho, dgates=dg, dc_ws=dcs[d])
         rows = Tc * N
         for c0 in range(0, T + Tc, Tc):
             if c0 >= Tc:    # layer 2 finished backward steps [c0-Tc, c0) = frames [T-c0, T-c0+Tc): dgrad into dh1
@@ -1231,15 +1235,8 @@ class LstmStack2Fn(torch.autograd.Function):
             dx = torch.empty((R, In), **f32)
             gemm(dg1, der[0].w_ih_t, dx, None, R, In, 4 * H, 4 * H, 4 * H, In, True, True, mode=mode)
         with side_work(x, h1, h2, dg1, dg2):
-            for dg, inp, hh, wi, wh, bi, bh in ((dg2, h1, h2, w_ih2, w_hh2, b_ih2, b_hh2),
-                                                (dg1, x, h1, w_ih1, w_hh1, b_ih1, b_hh1)):
-                linear_wgrad_acc(dg, inp, _grad_buf(wi), mode=mode, owner=_owner_of(wi))
-                gw = _grad_buf(wh)
-                rws = R - N
-                sk = _split_k(_tiles(4 * H, H), rws)
-                wgrad_gemm(dg.data_ptr() + esz * N * 4 * H, hh, gw, _owner_of(wh), 4 * H, H, rws, 4 * H, H, False, False, sk,
-                           mode, flags=(A_BF16 if s16 else 0) | (B_BF16 if hh.dtype == torch.bfloat16 else 0))
-                colsum_add(dg, _grad_buf(bi), _grad_buf(bh))
+            for dg, inp, hh, params in ((dg2, h1, h2, (w_ih2, w_hh2, b_ih2, b_hh2)), (dg1, x, h1, (w_ih1, w_hh1, b_ih1, b_hh1))):
+                _lstm_wgrad(dg, inp, hh, 0, H, params, T, N, H, 0, s16, mode, bias_done=False)
         _ready(w_ih2, w_hh2, b_ih2, b_hh2)
         _ready(w_ih1, w_hh1, b_ih1, b_hh1)
         del dcs

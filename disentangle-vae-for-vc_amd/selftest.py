@@ -6,7 +6,8 @@ rounds 4 and 5 one chip in fifty-nine showed wrong rows in a kernel form that ev
 Before a long training run on a new box, this runs every persistent kernel the product dispatches (default arithmetic: forward +
 both backward forms at H = 512 and H = 1024; bf16 mode: H = 512 and H = 1024, at T = 48 and at the T = 512 of BASELINE configs[4]) for `--rounds` rounds while a second stream
 streams 0 .. 4 GiB through HBM, and compares every output word with the one-launch-per-frame kernels of the same arithmetic and,
-bit for bit, with the first persistent round.  Exit code 0: all equal; 1: a mismatch (the report names kernel, tensor, round,
+bit for bit, with the first persistent round; the bias gradients, which the persistent backward launch leaves per row group in
+the dbias_part slabs as in training, against the column sums of that launch's own dgates.  Exit code 0: all equal; 1: a mismatch (the report names kernel, tensor, round,
 frame and rows, and the GPU's KFD unique_id); a failing box should train with DVAE_LSTM_PERSISTENT=0.
 """
 from __future__ import annotations
@@ -33,10 +34,13 @@ def gpu_unique_ids():
 
 
 def _pass(mode, H, T, N, pers, seed=0):
-    """forward + backward recurrence of one layer through the C ABI; returns (gates, c, h, dgates)"""
+    """forward + backward recurrence of one layer through the C ABI, with the descriptors and — persistent — the bias path of
+    the product (ops._lstm_dir, ops._pers_fill; bias gradients stored per row group into the dbias_part slabs, as
+    ops.pers_bias_slabs provides them); returns (gates, c, h, dgates, slabs): slabs [PERS_BIAS_SLABS, 4H], None for the
+    per-frame launches, which leave no bias gradient"""
     from . import _lib, ops
     from .derived import lstm_local
-    L, st, ptr = _lib.lib(), _lib.stream(), _lib.ptr
+    L, st = _lib.lib(), _lib.stream()
     bf = mode == _lib.MODE_BF16
     g = torch.Generator(device="cuda").manual_seed(1000 + seed)
     f = dict(device="cuda", dtype=torch.float32)
@@ -48,23 +52,43 @@ def _pass(mode, H, T, N, pers, seed=0):
     h = torch.full((T * N, H), float("nan"), device="cuda", dtype=sdt)
     c = torch.empty(T * N, H, **f)
     dg = torch.full((T * N, 4 * H), float("nan"), device="cuda", dtype=sdt)
-    dc, db = torch.empty(N, H, **f), torch.zeros(2, 4 * H, **f)
-    ws = ops.lstm_pers_workspace("cuda")
-    d = (_lib.LstmDir * 1)()
-    d[0].gates, d[0].c_all, d[0].h_out, d[0].w_hh, d[0].w_packed = ptr(gates), ptr(c), ptr(h), ptr(w_hh), ptr(der.pack_f)
-    d[0].packed_mode, d[0].state_bf16 = mode, int(bf)
-    b = (_lib.LstmDir * 1)()
-    b[0].gates, b[0].c_all, b[0].w_hh, b[0].w_packed = ptr(gates), ptr(c), ptr(der.w_hh_t), ptr(der.pack_b)
-    b[0].dh_out, b[0].dgates, b[0].dc_ws, b[0].packed_mode, b[0].state_bf16 = ptr(dh), ptr(dg), ptr(dc), mode, int(bf)
-    if pers:
-        ops._pers_claim("cuda")          # one persistent launch at a time per device, as every product call site
-        d[0].pers_ws = b[0].pers_ws = ptr(ws)
-        b[0].dbias_ih, b[0].dbias_hh = ptr(db[0]), ptr(db[1])
+    dc = torch.empty(N, H, **f)
+    part = torch.zeros(_lib.PERS_BIAS_SLABS, 4 * H, **f) if pers else None
+    d, b = (_lib.LstmDir * 1)(), (_lib.LstmDir * 1)()
+    common = dict(H=H, gates=gates, c_all=c, packed_mode=mode, state_bf16=bf)
+    ops._lstm_dir(d[0], w_hh=w_hh, w_packed=der.pack_f, h_out=h, **common)
+    ops._lstm_dir(b[0], w_hh=der.w_hh_t, w_packed=der.pack_b, dh_out=dh, dgates=dg, dc_ws=dc, **common)
+    if pers:                             # (claims the device: one persistent launch at a time, as every product call site)
+        ops._pers_fill(d[0], "cuda")
+        ops._pers_fill(b[0], "cuda", part)
     _lib.check(L.dvae_lstm_seq_fwd(d, 1, T, N, H, H, st), "fwd")
     _lib.check(L.dvae_lstm_seq_bwd(b, 1, T, N, H, H, st), "bwd")
     if pers:
         ops.lstm_pers_check()
-    return [t.float() for t in (gates, c, h, dg)]
+    return [t.float() for t in (gates, c, h, dg)] + [part]
+
+
+def _bias_slabs_wrong(slabs, dgates, T, N, first=None):
+    """What is wrong with the bias-gradient slabs of a persistent backward launch (None: nothing).  Held as
+    tests/lstm_ref.py bias_check holds them: slabs of row groups the launch cannot have (>= ceil(N/16)) exactly zero, and the
+    float64 sum over the slabs, per column, against the float64 column sum s of the launch's OWN dgates within
+    gamma(T*N + 16) * sum|dG| + eps32 * |s|, gamma(n) = n eps32 / (1 - n eps32) — T*N fp32 additions in whatever order plus
+    the 16 of the slab sum, and the rounding of the result; and bit for bit against the first good round (`first`)."""
+    if not bool(torch.isfinite(slabs).all()):
+        return "not finite"
+    if bool((slabs[-(-N // 16):] != 0).any()):
+        return f"a slab of a row group >= {-(-N // 16)}, which the launch does not have, is not zero"
+    eps32, n = 2.0 ** -24, T * N + 16
+    dg = dgates.double()
+    s = dg.sum(0)
+    bound = n * eps32 / (1.0 - n * eps32) * dg.abs_().sum(0) + eps32 * s.abs()
+    err = (slabs.double().sum(0) - s).abs()
+    if bool((err > bound).any()):
+        j = int((err - bound).argmax())
+        return f"column {j}: |sum of slabs - column sum of dgates| {float(err[j]):.3e} (bound {float(bound[j]):.3e})"
+    if first is not None and not torch.equal(slabs, first):
+        return "persistent rounds differ bitwise"
+    return None
 
 
 def run(rounds: int = 200, log=print) -> int:
@@ -91,7 +115,7 @@ def run(rounds: int = 200, log=print) -> int:
                 skipped += 1
                 continue
             ran += 1
-            ref = [t.clone() for t in _pass(mode, H, T, N, False)]
+            ref = _pass(mode, H, T, N, False)[:4]                   # (the per-frame launches leave no bias gradient)
             first, case_bad = None, 0
             n_rounds = rounds if T <= 128 else max(1, rounds // 4)      # the long sequences cost 4-8 x per round
             for rnd in range(n_rounds):
@@ -120,6 +144,11 @@ def run(rounds: int = 200, log=print) -> int:
                         case_bad += 1
                         clean = False
                         break
+                why = _bias_slabs_wrong(got[4], got[3], T, N, None if first is None else first[4]) if clean else None
+                if why:
+                    log(f"MISMATCH {name} H={H} N={N}: dbias_part, round {rnd} ({rnd % 5} GiB of foreign traffic): {why}")
+                    case_bad += 1
+                    clean = False
                 if first is None and clean:              # the bitwise reference is a round that matched the frame kernels
                     first = [t.clone() for t in got]
             torch.cuda.synchronize()

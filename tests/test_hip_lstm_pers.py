@@ -447,6 +447,30 @@ def test_workspace_size_contract(env):
         assert L.dvae_lstm_pers_ws_bytes(N, H) <= ops.lstm_pers_workspace("cuda").numel()
 
 
+@pytest.mark.parametrize("mode,H,T,N", [("fp32x3", 512, 3, 40),      # three row groups of 16, the last ragged; dead slabs above
+                                         ("bf16", 512, 3, 128)])     # eight full row groups, bf16 dgates
+def test_selftest_pass_leaves_the_products_bias_slabs(env, mode, H, T, N):
+    """selftest._pass drives the persistent backward launch as the product does — descriptors from ops._lstm_dir, bias
+    gradients stored per row group into dbias_part — and returns the slabs: held by lstm_ref.bias_check against the
+    launch's own dgates (float64 slab sum within gamma(T N + 16) sum|dG| + eps32 |s|; slabs of row groups the launch does
+    not have exactly zero)."""
+    import lstm_ref as R
+    from dvae_amd import selftest
+    _lib, ops, _ = env
+    ops.set_compute_dtype(mode)
+    m = _lib.COMPUTE_MODES[mode]
+    if not (ops.lstm_persistent_usable(N, H, m) and ops.lstm_persistent_usable(N, H, m, bwd=True)):
+        pytest.skip("no persistent launch for this shape on this device")
+    out = selftest._pass(m, H, T, N, pers=True)
+    assert len(out) == 5 and tuple(out[4].shape) == (_lib.PERS_BIAS_SLABS, 4 * H)
+    dG = out[3].cpu().numpy().reshape(T, N, 4 * H)
+    res = R.bias_check(dG, None, None, slabs=out[4].cpu().numpy())
+    for k, (ratio, col) in res.items():
+        print(f"{mode} H={H} T={T} N={N}: {k} ratio {ratio:.3f} (column {col})")
+    assert set(res) == {"dbias_part", "dbias_part_zero_rows"}
+    assert all(r <= 1.0 for r, _ in res.values()), res
+    assert selftest._pass(m, H, T, N, pers=False)[4] is None           # the per-frame launches leave no bias gradient
+
 
 def test_deployment_selftest_passes_here(env):
     """dvae_amd.selftest (the check to run on a new box before a long training run): every product persistent kernel against

@@ -266,6 +266,100 @@ def test_stacked_lstm_schedule_rules():
     assert not S.usable(1, 1024, 2, False) and not S.usable(127, 1024, 2, False)
 
 
+def test_lstm_dir_builder_writes_every_field_at_literal_addresses():
+    """ops._lstm_dir is the one place that fills a dvae_lstm_dir_t: every field against literal `base + bytes` for each layout
+    the product reaches.  A kernel trusts its descriptor, so one wrong factor here is a silently wrong gradient or a write out
+    of range; nothing else sees these offsets.  Pure host code: CPU tensors stand in for the device's."""
+    import dvae_amd  # noqa: F401
+    from dvae_amd import _lib, ops
+    names = [n for n, _ in _lib.LstmDir._fields_]
+    f32, b16 = torch.float32, torch.bfloat16
+
+    def entry():
+        e = _lib.LstmDir()
+        for n in names:                                   # stale values everywhere: the builder must overwrite each field
+            setattr(e, n, 0x7f7f)
+        return e
+
+    def fields(e):
+        return {n: getattr(e, n) or 0 for n in names}     # (a NULL pointer reads back as None)
+
+    def want(**kw):
+        assert set(kw) <= set(names), set(kw) - set(names)
+        return dict({n: 0 for n in names}, **kw)          # fields not given: 0 / NULL, pers_ws and dbias_* among them
+
+    def base(t):
+        assert t.data_ptr() != 0
+        return t.data_ptr()
+
+    # one direction, fp32 state (dec_lstm1: H = 512), forward
+    H, R = 512, 3
+    g, c, h = torch.zeros(R, 4 * H), torch.zeros(R, H), torch.zeros(R, H)
+    w, pk = torch.zeros(4 * H, H), torch.zeros(7)
+    e = entry()
+    ops._lstm_dir(e, H=H, d=0, gates=g, gate_ld=4 * H, w_hh=w, w_packed=pk, packed_mode=2, c_all=c, state_bf16=False,
+                  reverse=0, h_out=h)
+    assert fields(e) == want(gates=base(g), gate_ld=2048, w_hh=base(w), w_packed=base(pk), packed_mode=2, c_all=base(c),
+                             h_out=base(h))
+
+    # two directions, H = 64, gates side by side in one [R, 8H] tensor, state in one [R, 2H] tensor: forward and backward
+    H = 64
+    gall, dgall = torch.zeros(R, 512), torch.zeros(R, 512)
+    h, dh = torch.zeros(R, 128), torch.zeros(R, 128)
+    cs, dcs = [torch.zeros(R, H) for _ in range(2)], [torch.zeros(2, H) for _ in range(2)]
+    wt = torch.zeros(H, 4 * H)
+    for d, (gate_bytes, state_bytes) in enumerate(((0, 0), (1024, 256))):      # 4 * d * 4H and 4 * d * H bytes
+        e = entry()
+        ops._lstm_dir(e, H=H, d=d, gates=gall, gate_ld=8 * H, w_hh=w, w_packed=pk, packed_mode=0, c_all=cs[d],
+                      state_bf16=False, reverse=d, h_out=h)
+        assert fields(e) == want(gates=base(gall) + gate_bytes, gate_ld=512, w_hh=base(w), w_packed=base(pk),
+                                 c_all=base(cs[d]), h_out=base(h) + state_bytes, reverse=d)
+        e = entry()
+        ops._lstm_dir(e, H=H, d=d, gates=gall, gate_ld=8 * H, w_hh=wt, w_packed=pk, packed_mode=0, c_all=cs[d],
+                      state_bf16=False, reverse=d, dh_out=dh, dgates=dgall, dc_ws=dcs[d])
+        assert fields(e) == want(gates=base(gall) + gate_bytes, gate_ld=512, w_hh=base(wt), w_packed=base(pk),
+                                 c_all=base(cs[d]), dh_out=base(dh) + state_bytes, dgates=base(dgall) + gate_bytes,
+                                 dc_ws=base(dcs[d]), reverse=d)
+
+    # bf16 state, two directions with gates of their own (gate_ld = 4H: no gate column offset): h_out counts 2-byte
+    # elements, dh_out 4-byte ones; the backward form has W_hh^T, the backward pack, dc_ws and dgates, and NO h_out
+    H = 512
+    g1, dg1 = torch.zeros(R, 4 * H), torch.zeros(R, 4 * H, dtype=b16)
+    h, dh = torch.zeros(R, 2 * H, dtype=b16), torch.zeros(R, 2 * H, dtype=f32)
+    c, dc, wt, pkb = torch.zeros(R, H), torch.zeros(2, H), torch.zeros(H, 4 * H), torch.zeros(5)
+    e = entry()
+    ops._lstm_dir(e, H=H, d=1, gates=g1, gate_ld=4 * H, w_hh=w, w_packed=pk, packed_mode=1, c_all=c, state_bf16=True,
+                  reverse=1, h_out=h)
+    assert fields(e) == want(gates=base(g1), gate_ld=2048, w_hh=base(w), w_packed=base(pk), packed_mode=1, c_all=base(c),
+                             h_out=base(h) + 1024, reverse=1, state_bf16=1)
+    e = entry()
+    ops._lstm_dir(e, H=H, d=1, gates=g1, gate_ld=4 * H, w_hh=wt, w_packed=pkb, packed_mode=1, c_all=c, state_bf16=True,
+                  reverse=1, dh_out=dh, dgates=dg1, dc_ws=dc)
+    assert fields(e) == want(gates=base(g1), gate_ld=2048, w_hh=base(wt), w_packed=base(pkb), packed_mode=1, c_all=base(c),
+                             dh_out=base(dh) + 2048, dgates=base(dg1), dc_ws=base(dc), reverse=1, state_bf16=1)
+
+    # a stacked pair (LstmStack2Fn): every layer owns its tensors, gate_ld left at 0 (= 4H), step_shift = (0, Tc);
+    # integer addresses are taken as they are
+    Tc = 4
+    for d, shift in enumerate((0, Tc)):
+        e = entry()
+        ops._lstm_dir(e, H=H, gates=g1, w_hh=w, w_packed=pk, packed_mode=2, c_all=c, state_bf16=False,
+                      step_shift=Tc if d == 1 else 0, h_out=base(h) + 64)
+        assert fields(e) == want(gates=base(g1), w_hh=base(w), w_packed=base(pk), packed_mode=2, c_all=base(c),
+                                 h_out=base(h) + 64, step_shift=shift)
+        e = entry()
+        ops._lstm_dir(e, H=H, gates=g1, w_hh=wt, w_packed=pkb, packed_mode=2, c_all=c, state_bf16=False,
+                      step_shift=Tc if d == 1 else 0, dh_out=dh, dgates=dg1, dc_ws=dc)
+        assert fields(e) == want(gates=base(g1), w_hh=base(wt), w_packed=base(pkb), packed_mode=2, c_all=base(c),
+                                 dh_out=base(dh), dgates=base(dg1), dc_ws=base(dc), step_shift=shift)
+
+    # the shifted operands of the W_hh gradient (h_prev of frame t: h[t-1] forward, h[t+1] reverse), N = 5 rows per frame
+    N = 5
+    assert ops._lstm_hprev(dg1, h, 0, N, H, 4 * H, 2 * H, 2, reverse=0) == (base(dg1) + 2 * 5 * 2048, base(h))
+    assert ops._lstm_hprev(dg1, h, 1, N, H, 4 * H, 2 * H, 2, reverse=1) == (base(dg1), base(h) + 2 * (5 * 1024 + 512))
+    assert ops._lstm_hprev(1 << 20, 1 << 21, 1, N, 64, 512, 128, 4, reverse=1) == (1 << 20, (1 << 21) + 4 * (5 * 128 + 64))
+
+
 def test_frontend_refuses_cpu():
     import dvae_amd  # noqa: F401
     from dvae_amd.frontend import MelFrontend
