@@ -61,7 +61,7 @@ COMPUTE_MODES = {"fp32": MODE_F32, "f32": MODE_F32, "float32": MODE_F32, "bf16":
                  "fp32x3": MODE_F32X3, "f32x3": MODE_F32X3}
 
 DEFAULT_COMPUTE_DTYPE = "fp32x3"
-ABI_VERSION = 317    # DVAE_ABI_VERSION of include/dvae_hip.h
+ABI_VERSION = 318    # DVAE_ABI_VERSION of include/dvae_hip.h
 
 # name -> (restype, argtypes); mirrors include/dvae_hip.h one to one
 SIGNATURES = {
@@ -158,6 +158,7 @@ SIGNATURES = {
     "dvae_resample_lds_floats": (i32, [i64, i64, i32]),
     "dvae_resample_batch": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "dvae_volume_normalize": (i32, [vp, vp, i32, vp, i32, vp, vp, C.c_double, i32, vp, vp, vp, vp]),
+    "dvae_vad_trim": (i32, [vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dvae_stft_frames_seg": (i32, [vp, vp, i32, i64, vp, vp, i32, i32, i32, vp]),
     "dvae_mel_db_normalize_seg": (i32, [vp, vp, vp, i32, i64, i32, f32, f32, f32, vp]),
     "dvae_log_power": (i32, [vp, vp, vp, i64, i32, i32, f32, vp]),

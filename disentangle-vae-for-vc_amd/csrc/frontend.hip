@@ -951,14 +951,22 @@ DVAE_API int dvae_volume_normalize(float* y, const int64_t* segs, int nseg, cons
   if (!y || !segs || !tiles || !tile_first || !part || !gain || !silent || nseg < 1 || ntiles < 1 ||
       !(target_dbfs < 1e3 && target_dbfs > -1e3))
     return DVAE_EINVAL;
-  hipLaunchKernelGGL(sumsq_tiles_kernel, dim3((unsigned)ntiles), dim3(NV_THREADS), 0, (hipStream_t)stream, y, segs, tiles,
-                     part);
-  int rc = dvae_check_launch();
+  int rc;
+  {
+    ProfScope prof(DVAE_PROF_AUDIO, (hipStream_t)stream, 0.0, 0);
+    hipLaunchKernelGGL(sumsq_tiles_kernel, dim3((unsigned)ntiles), dim3(NV_THREADS), 0, (hipStream_t)stream, y, segs, tiles,
+                       part);
+    rc = dvae_check_launch();
+  }
   if (rc) return rc;
-  hipLaunchKernelGGL(volume_finalize_kernel, dim3((unsigned)((nseg + 127) / 128)), dim3(128), 0, (hipStream_t)stream,
-                     segs, nseg, tile_first, part, target_dbfs, increase_only, ms_out, gain, silent);
-  rc = dvae_check_launch();
+  {
+    ProfScope prof(DVAE_PROF_AUDIO, (hipStream_t)stream, 0.0, 1);
+    hipLaunchKernelGGL(volume_finalize_kernel, dim3((unsigned)((nseg + 127) / 128)), dim3(128), 0, (hipStream_t)stream,
+                       segs, nseg, tile_first, part, target_dbfs, increase_only, ms_out, gain, silent);
+    rc = dvae_check_launch();
+  }
   if (rc) return rc;
+  ProfScope prof(DVAE_PROF_AUDIO, (hipStream_t)stream, 0.0, 2);
   hipLaunchKernelGGL(volume_scale_kernel, dim3((unsigned)ntiles), dim3(NV_THREADS), 0, (hipStream_t)stream, y, segs, tiles,
                      gain);
   return dvae_check_launch();
@@ -1054,3 +1062,6 @@ DVAE_API int dvae_f0_viterbi(const float* r, int ldr, int nlag, const float* gai
                      voiced, segs, l2, oct, jump_cost, sample_rate, lag_min, back, lag, f0, lf0v);
   return dvae_check_launch();
 }
+
+// ---- silence trimming: the kernels behind dvae_vad_trim, part of this translation unit
+#include "vad.hip"

@@ -1,7 +1,7 @@
 """Corpus preprocessing on the GPU: a VCTK `.wav` tree -> the mel corpus `<out>/<speaker>/*_mel.npy` that
 `SpeechDatasetGVAE` / `GpuPairLoader` read.  The reference's `preprocessing.sh` step:
 
-    python -m dvae_amd.preprocess <datasets_root> [-o OUT] [-d VCTK] [-s] [--no_trim] [--batch-seconds S] [--workers W]
+    python -m dvae_amd.preprocess <datasets_root> [-o OUT] [-d VCTK] [-s] (--no_trim | --trim) [--batch-seconds S] [--workers W]
 
 mirrors the reference's preprocessing/dataset_preprocess.py -> encoder/preprocess.py:78-138,153-170 -> encoder/audio.py:22-51
 `preprocess_wav`:
@@ -9,6 +9,7 @@ mirrors the reference's preprocessing/dataset_preprocess.py -> encoder/preproces
     librosa.load(path, sr=None, duration=600)           read_wav (numpy RIFF reader; float32 mono, first 600 s)
     librosa.resample(wav, sr, 16000)                     resampy kaiser_best (fix=True: ceil(n * 16000 / sr) samples)
     normalize_volume(wav, -30, increase_only=True)       float64 mean square, gain only where it is > 1
+    trim_long_silences(wav)            (--trim only)     window energies, per-utterance threshold, the reference's smoothing
     wav_to_mel_spectrogram -> np.save([80, M])           MelFrontend, pinned: one k-split, segmented passes
 
 One launch per pass for a whole batch of utterances (any source rates and lengths, packed back to back), all on one stream;
@@ -19,8 +20,9 @@ resampy and librosa are not dependencies: the kaiser_best filter is restated fro
 (`sinc_window(64, 9, kaiser(14.769656459379492), rolloff=0.9475937167399596)`, resampy/interp.py `resample_f`) and its
 parity with the real package is UNPINNED.  Differences from the reference, on purpose: the corpus is
 float32 (the reference wrote float64 from lws; float32 carries every bit computed here); a silent file is skipped and
-reported (the reference wrote a NaN mel); there is no VAD (webrtcvad is absent, so --no_trim is required, as the reference
-requires it when webrtcvad does not import).  Kept on purpose: the reference's `len(frames) < partials_n_frames` test never
+reported (the reference wrote a NaN mel); webrtcvad is absent, so without a flag the tool stops as the reference does when
+webrtcvad does not import: --no_trim builds the corpus untrimmed, --trim trims with the energy detector of vad_packed below
+(this project's own; its parity with webrtcvad is UNPINNED).  Kept on purpose: the reference's `len(frames) < partials_n_frames` test never
 fires (`frames` is [80, M], len 80), so every decodable utterance is written however short.
 """
 from __future__ import annotations
@@ -45,6 +47,14 @@ SAMPLE_RATE = 16000
 RESAMPLE_TILE = 256           # DVAE_RESAMPLE_TILE
 VOLUME_TILE = 2048            # DVAE_VOLUME_TILE
 KAISER_BEST = dict(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596)
+VAD_WINDOW = 480              # DVAE_VAD_WINDOW: 30 ms at 16 kHz (audio.py vad_window_length)
+VAD_MA_WIDTH = 8              # DVAE_VAD_MA_WIDTH (vad_moving_average_width)
+VAD_MAX_SILENCE = 6           # DVAE_VAD_MAX_SILENCE (vad_max_silence_length)
+VAD_PREEMPH = 0.97            # DVAE_VAD_PREEMPH
+VAD_BINS, VAD_BIN_OFFSET = 96, 80                                 # b = clamp(ilogb(E) + 80, 0, 95)
+VAD_BIN_FLOOR, VAD_BIN_ABOVE_P10, VAD_BIN_BELOW_P90 = 66, 3, 5    # t = max(66, min(b10 + 3, b90 - 5))
+TOO_SHORT_TO_TRIM = "shorter than one 30 ms window"
+NO_SPEECH = "no speech detected"
 DATASETS = ("VCTK",)
 NO_TRIM_MESSAGE = ("Package 'webrtcvad' not found. This package enables noise removal and is recommended. Please install "
                    "and try again. If installation fails, use --no_trim to disable this error message.")
@@ -350,6 +360,69 @@ def normalize_volume_batch(wavs: Sequence, target_dbfs=-30.0, increase_only=True
     return [y[int(o):int(o + n)] for o, n in zip(table[:, 2], table[:, 3])], silent
 
 
+def vad_prepare(table, device) -> dict:
+    """the host side of dvae_vad_trim: the window map {segment, w} of `table`'s segments and each segment's first window in
+    it, on the device, with the per-window and per-segment outputs"""
+    table = np.ascontiguousarray(table, dtype=np.int64)
+    nseg = len(table)
+    W = table[:, 3] // VAD_WINDOW
+    first = np.concatenate([[0], np.cumsum(W)]).astype(np.int64)
+    nwin = int(first[-1])
+    wins = np.zeros((nwin, 2), dtype=np.int64)
+    wins[:, 0] = np.repeat(np.arange(nseg, dtype=np.int64), W)
+    wins[:, 1] = np.arange(nwin, dtype=np.int64) - np.repeat(first[:-1], W)
+    to = lambda a: upload(a, device, np.int64)
+    i32 = lambda n: torch.empty(max(1, n), device=device, dtype=torch.int32)
+    return dict(nseg=nseg, nwin=nwin, W=W, first=first, table=table, segs=to(table), wins=to(wins), win_first=to(first),
+                E=torch.empty(max(1, nwin), device=device, dtype=torch.float64), bins=i32(nwin), flags=i32(nwin),
+                keep=i32(nwin), dst=i32(nwin), t=i32(nseg), K=i32(nseg))
+
+
+def vad_launch(y, prep: dict, out, want=()):
+    """dvae_vad_trim alone (three launches, no sync): the kept windows of y's segments back to back in `out`, at the
+    segments' own offsets; results stay in prep["K" | "keep" | "dst" | "bins"] and, where `want` names them, in
+    prep["E" | "flags" | "t"]"""
+    opt = lambda k: ptr(prep[k]) if k in want else None
+    check(lib().dvae_vad_trim(ptr(y), ptr(out), prep["table"].ctypes.data, ptr(prep["segs"]), prep["nseg"],
+                              ptr(prep["wins"]), prep["nwin"], ptr(prep["win_first"]), opt("E"), ptr(prep["bins"]),
+                              opt("flags"), ptr(prep["keep"]), ptr(prep["dst"]), opt("t"), ptr(prep["K"]), stream()),
+          "dvae_vad_trim")
+
+
+def vad_packed(y, table, want=()):
+    """trim_long_silences (audio.py:78-118) on the packed segments of `table` ({.., out0, n_out, ..} columns 2, 3), after
+    volume normalisation, with the energy detector of include/dvae_hip.h ("silence trimming") in webrtcvad's place ->
+    (out: a second device buffer with segment s's 480 K[s] kept samples at out0[s], the rest of it unwritten;
+     K [nseg] numpy: the one device-to-host copy and sync;
+     extras: `first` ([nseg + 1] numpy, segment s owns windows first[s] .. first[s + 1]) and the device tensors that `want`
+     names of "E" (float64), "flags", "keep" (int32) per window and "t" (int32) per segment)"""
+    bad = set(want) - {"E", "flags", "keep", "t"}
+    if bad:
+        raise ValueError(f"vad_packed: unknown outputs {sorted(bad)}")
+    prep = vad_prepare(table, y.device)
+    out = torch.empty_like(y)
+    if prep["nseg"]:
+        vad_launch(y, prep, out, want)
+    K = prep["K"][:prep["nseg"]].cpu().numpy()
+    extras = {k: prep[k][:prep["nseg" if k == "t" else "nwin"]] for k in want}
+    extras["first"] = prep["first"]
+    return out, K, extras
+
+
+def trim_long_silences_batch(wavs: Sequence, device="cuda"):
+    """trim_long_silences(wav) of every (volume-normalised, 16 kHz) utterance, one pass for all -> (list of 1-D device fp32
+    tensors of 480 K[i] samples, K [n] numpy).  K[i] == 0: shorter than one window, or nothing detected."""
+    arrs = [flat(w) for w in wavs]
+    if not arrs:
+        return [], np.zeros(0, dtype=np.int32)
+    y, offs = pack(arrs, device)
+    table = np.zeros((len(arrs), 6), dtype=np.int64)
+    table[:, 2] = offs
+    table[:, 3] = [a.shape[0] for a in arrs]
+    out, K, _ = vad_packed(y, table)
+    return [out[int(o):int(o) + VAD_WINDOW * int(k)] for o, k in zip(offs, K)], K
+
+
 # ------------------------------------------------------------------------------------------------------------------ CLI
 def _parse(argv):
     p = argparse.ArgumentParser(prog="python -m dvae_amd.preprocess",
@@ -361,7 +434,10 @@ def _parse(argv):
     p.add_argument("-d", "--datasets", type=str, default="VCTK", help="comma-separated dataset names (supported: VCTK)")
     p.add_argument("-s", "--skip_existing", action="store_true",
                    help="skip files already listed in <speaker>/_sources.txt (resume an interrupted run)")
-    p.add_argument("--no_trim", action="store_true", help="preprocess without VAD silence trimming (required: no VAD here)")
+    p.add_argument("--no_trim", action="store_true",
+                   help="preprocess without silence trimming (one of --no_trim / --trim is required: no webrtcvad here)")
+    p.add_argument("--trim", action="store_true",
+                   help="trim long silences with the energy detector on the GPU (not webrtcvad: parity unpinned)")
     p.add_argument("--batch-seconds", type=float, default=1200.0,
                    help="seconds of 16 kHz output per GPU batch (a longer file goes alone); does not change any output")
     p.add_argument("--workers", type=int, default=8, help="host threads that decode and write (at most 16)")
@@ -375,8 +451,12 @@ def main(argv=None) -> int:
     if unknown or not names:
         print(f"preprocess: unsupported dataset(s) {unknown or names}; supported: {', '.join(DATASETS)}", file=sys.stderr)
         return 2
-    if not args.no_trim:                               # dataset_preprocess.py:42-50; no VAD package here
-        print(f"preprocess: ModuleNotFoundError: {NO_TRIM_MESSAGE}", file=sys.stderr)
+    if args.trim and args.no_trim:
+        print("preprocess: --trim and --no_trim exclude each other: choose one", file=sys.stderr)
+        return 2
+    if not args.no_trim and not args.trim:             # dataset_preprocess.py:42-50; no VAD package here
+        print(f"preprocess: ModuleNotFoundError: {NO_TRIM_MESSAGE}\n"
+              "preprocess: or use --trim for the energy-based trimming built into this tool.", file=sys.stderr)
         return 2
     if args.batch_seconds <= 0:
         print("preprocess: --batch-seconds must be > 0", file=sys.stderr)
@@ -388,21 +468,26 @@ def main(argv=None) -> int:
         print(f"preprocess: {dataset_root} does not exist", file=sys.stderr)
         return 2
     out_dir.mkdir(exist_ok=True, parents=True)
-    stats = preprocess_vctk(dataset_root, out_dir, args.skip_existing, args.batch_seconds, workers)
+    stats = preprocess_vctk(dataset_root, out_dir, args.skip_existing, args.batch_seconds, workers, trim=args.trim)
     skipped = stats["skipped"]
-    print(f"preprocess: {stats['written']} written, {stats['existing']} already present, {len(skipped)} skipped"
+    trimmed = ""
+    if "trimmed_samples" in stats:
+        trimmed = f"; trimmed {stats['trimmed_samples'] / SAMPLE_RATE:.1f} s of {stats['total_samples'] / SAMPLE_RATE:.1f} s"
+    print(f"preprocess: {stats['written']} written, {stats['existing']} already present, {len(skipped)} skipped" + trimmed
           + "".join(f"; {p} ({why})" for p, why in skipped))
     return 0
 
 
 def preprocess_vctk(dataset_root: Path, out_dir: Path, skip_existing=False, batch_seconds=1200.0, workers=8,
-                    run_batch=None, decode_ahead=None) -> dict:
+                    run_batch=None, decode_ahead=None, trim=False) -> dict:
     """encoder/preprocess.py:78-138 on the sorted speaker directories of `dataset_root`, in one ordered stream of
     batches over all speakers, pipelined: `workers` threads decode at most `decode_ahead` (default 4 x workers) files
     ahead of the batch being filled; each batch is resampled, normalised and turned into mels on the GPU (`run_batch`,
     default the HIP passes) while the next files decode; a separate writer pool saves it while the next batch runs, and a
     batch's `_sources.txt` lines follow once its files are on disk.  Host memory is bounded by the decode window, the
-    batch being filled and the batch being written, whatever the corpus size."""
+    batch being filled and the batch being written, whatever the corpus size.  `trim` selects the default runner's
+    silence trimming (an injected `run_batch` does its own); where the runner counts them (`trim_stats`), the samples it
+    saw and trimmed come back as total_samples / trimmed_samples."""
     speakers = sorted(d for d in dataset_root.iterdir() if d.is_dir())
     items, sources = [], {}
     existing_count = 0
@@ -426,7 +511,7 @@ def preprocess_vctk(dataset_root: Path, out_dir: Path, skip_existing=False, batc
     ahead = max(1, decode_ahead if decode_ahead is not None else 4 * workers)
     try:
         if items and run_batch is None:
-            run_batch = _gpu_runner()
+            run_batch = _gpu_runner(trim)
         with ThreadPoolExecutor(max_workers=workers) as decoders, \
                 ThreadPoolExecutor(max_workers=max(1, min(4, workers))) as writers:
             queue = deque()                            # decode futures in file order, at most `ahead` of them
@@ -485,27 +570,50 @@ def preprocess_vctk(dataset_root: Path, out_dir: Path, skip_existing=False, batc
     finally:
         for fh in sources.values():
             fh.close()
-    return dict(written=written, existing=existing_count, skipped=skipped)
+    stats = dict(written=written, existing=existing_count, skipped=skipped)
+    counts = getattr(run_batch, "trim_stats", None)
+    if counts is not None:
+        stats.update(total_samples=counts["total"], trimmed_samples=counts["total"] - counts["kept"])
+    return stats
 
 
 def _save(path, mel):
     np.save(path, mel)
 
 
-def _gpu_runner():
+def _gpu_runner(trim=False):
     fe, rs = MelFrontend(), Resampler()
-    return lambda wavs, srs: _run_batch(fe, rs, wavs, srs)
+    if not trim:
+        return lambda wavs, srs: _run_batch(fe, rs, wavs, srs)
+    counts = dict(total=0, kept=0)                     # 16 kHz samples of the utterances written, before and after trimming
+
+    def run(wavs, srs):
+        return _run_batch(fe, rs, wavs, srs, trim=True, counts=counts)
+
+    run.trim_stats = counts
+    return run
 
 
-def _run_batch(fe, rs: Resampler, wavs, srs):
-    """one batch: resample -> normalise -> mel on the current stream -> list of ([80, M] float32 numpy | None, reason)"""
+def _run_batch(fe, rs: Resampler, wavs, srs, trim=False, counts=None):
+    """one batch: resample -> normalise [-> trim] -> mel on the current stream -> list of ([80, M] float32 numpy | None,
+    reason).  trim: the mel runs on the compacted buffer of vad_packed, 480 K samples per utterance; K == 0 is skipped."""
     x, _ = pack(wavs, fe.device)
     y, table = rs.packed(x, [w.shape[0] for w in wavs], srs)
     _, _, silent = volume_packed(y, table)
-    keep = [i for i in range(len(wavs)) if not silent[i]]
     out = [(None, "silent")] * len(wavs)
+    lengths = table[:, 3]
+    if trim:
+        y, K, _ = vad_packed(y, table)
+        lengths = VAD_WINDOW * K.astype(np.int64)
+        for i in range(len(wavs)):
+            if not silent[i] and K[i] == 0:
+                out[i] = (None, TOO_SHORT_TO_TRIM if table[i, 3] < VAD_WINDOW else NO_SPEECH)
+    keep = [i for i in range(len(wavs)) if not silent[i] and lengths[i] > 0]
+    if counts is not None:
+        counts["total"] += int(table[keep, 3].sum())
+        counts["kept"] += int(lengths[keep].sum())
     if keep:
-        packed, ms = fe.mel_packed(y, table[keep, 2], table[keep, 3])
+        packed, ms = fe.mel_packed(y, table[keep, 2], lengths[keep])
         for i, m in zip(keep, fe.unpack(packed.cpu().numpy(), ms)):
             out[i] = (m, None)
     return out

@@ -45,7 +45,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 317
+#define DVAE_ABI_VERSION 318
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -602,6 +602,49 @@ int dvae_stft_frames_seg(const float* wav, const int64_t* segs, int nseg, int64_
 int dvae_mel_db_normalize_seg(const float* mel, float* out, const int64_t* segs, int nseg, int64_t rows, int n_mels,
                               float min_level, float ref_level_db, float min_level_db, void* stream);
 
+/* ---- silence trimming (python -m dvae_amd.preprocess --trim): the stage of audio.py:78-118 `trim_long_silences` between
+ * dvae_volume_normalize and the mel, on the same packed batch (segs[nseg][6], columns 2, 3 = out0, n_out; out0 a multiple
+ * of 4).  The reference asks webrtcvad, window by window; that package's sub-band GMM is not restated here, so the
+ * detector below is this project's own and its parity with webrtcvad is UNPINNED.  The smoothing
+ * and the dilation around it are the reference's (moving average of 8, np.round, binary_dilation with ones(6 + 1)),
+ * restated on integers.  Per utterance of n = n_out samples y:
+ *   W = n / 480 windows of 30 ms (DVAE_VAD_WINDOW); the n % 480 samples behind them are dropped
+ *   E_w = sum of the window's (y[i] - 0.97 y[i-1])^2 in float64 (DVAE_VAD_PREEMPH; y[-1] = 0 at the utterance's first
+ *         sample only, the predecessor crosses window borders), 8 consecutive samples per lane in index order, then a
+ *         fixed tree over the wave
+ *   b_w = clamp(ilogb(E_w) + DVAE_VAD_BIN_OFFSET, 0, DVAE_VAD_BINS - 1), read from the exponent field (zero and
+ *         subnormal E_w: 0)
+ *   c(b) = windows with b_w <= b; b10 / b90 the smallest b with c(b) >= ceil(W / 10) / ceil(9 W / 10)
+ *   t = max(DVAE_VAD_BIN_FLOOR, min(b10 + DVAE_VAD_BIN_ABOVE_P10, b90 - DVAE_VAD_BIN_BELOW_P90));  flag_w = b_w >= t
+ *   mask_w = more than half of the DVAE_VAD_MA_WIDTH flags of [w - 3, w + 4] set (5 of 8; np.round(4 / 8) is 0)
+ *   keep_w = any mask of [w - 3, w + 3] (DVAE_VAD_MAX_SILENCE + 1 wide); flags and masks outside [0, W) are 0
+ *   dst_w = kept windows before w;  K = kept windows in all
+ *   out[out0 + 480 dst_w + i] = y[out0 + 480 w + i] for every kept w: the kept windows back to back, 480 K samples, at
+ *         the segment's own offset of a second buffer.  480 K is a multiple of 4, so there are no pad floats behind it;
+ *         nothing else of `out` is written.
+ * Three launches for the batch on `stream` (energies: a wave per window; mask: a workgroup per utterance, chunked over
+ * any W; compaction: a wave per kept window), no floating-point atomics, one writer per element, nothing passed between
+ * workgroups: an utterance's bits depend on that utterance alone.  Everything behind E_w is integer logic.
+ * wins[nwin][2] = {segment, w} lists every window of the batch, segment by segment; win_first[nseg + 1] is the index of
+ * each segment's first window in it (both int64, in device memory, built by the caller; the kernels ignore an entry that
+ * does not fit segs).  Per window, at its index in wins: E (float64, optional), bins, flags (optional), keep, dst (int32);
+ * per segment: t (optional), K (int32).  segs_host is the host's copy of segs, read before the launches.
+ * DVAE_EINVAL, nothing launched: nseg < 0, nwin != sum of n_out / 480, a required pointer null, y == out, y or out not
+ * 16-byte aligned, another pointer not aligned to its element, an out0 that is negative or no multiple of 4, n_out < 0.
+ * nseg == 0 is a no-op. */
+#define DVAE_VAD_WINDOW 480
+#define DVAE_VAD_MA_WIDTH 8
+#define DVAE_VAD_MAX_SILENCE 6
+#define DVAE_VAD_PREEMPH 0.97
+#define DVAE_VAD_BINS 96
+#define DVAE_VAD_BIN_OFFSET 80
+#define DVAE_VAD_BIN_FLOOR 66
+#define DVAE_VAD_BIN_ABOVE_P10 3
+#define DVAE_VAD_BIN_BELOW_P90 5
+int dvae_vad_trim(const float* y, float* out, const int64_t* segs_host, const int64_t* segs, int nseg, const int64_t* wins,
+                  int64_t nwin, const int64_t* win_first, double* E, int* bins, int* flags, int* keep, int* dst, int* t,
+                  int* K, void* stream);
+
 /* ---- mel-cepstral distortion (python -m dvae_amd.evaluate): preprocessing/MCD_calculate.py:54-103 `evaluate_mcd_wav`
  * (WORLD mel-cepstra of the voiced frames, fastdtw, mean frame distance along the path) restated on a packed batch
  * (DESIGN.md §4.6).  The three contractions of the feature pass are dvae_gemm_f32 launches (fp32, unsplit); these are the
@@ -736,8 +779,10 @@ int dvae_group_sum_f64(const float* rows, const int* group, int P, int K, int G,
                        void* stream);
 
 /* ---- opt-in per-family kernel timing with HIP events on the launch stream (bench.py roofline) ----
- * family: 0 = off, 1 = GEMM/conv contraction kernel, 2 = LSTM step kernels.
+ * family: 0 = off, 1 = GEMM/conv contraction kernel, 2 = LSTM step kernels, 3 (DVAE_PROF_AUDIO) = the launches of
+ * dvae_volume_normalize (tags 0, 1, 2 in launch order) and of dvae_vad_trim (tags 3, 4, 5), for scripts/vad_cost.py.
  * dvae_prof_collect: synchronises the recorded events, returns total ms, launch count and algorithmic FLOPs. */
+#define DVAE_PROF_AUDIO 3
 int dvae_prof_enable(int family);
 int dvae_prof_collect(double* total_ms, int64_t* launches, double* flops);
 /* the same, split by kernel instantiation (call BEFORE dvae_prof_collect, which resets).  Contraction family: tag =
