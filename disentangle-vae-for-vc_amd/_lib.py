@@ -61,7 +61,7 @@ COMPUTE_MODES = {"fp32": MODE_F32, "f32": MODE_F32, "float32": MODE_F32, "bf16":
                  "fp32x3": MODE_F32X3, "f32x3": MODE_F32X3}
 
 DEFAULT_COMPUTE_DTYPE = "fp32x3"
-ABI_VERSION = 318    # DVAE_ABI_VERSION of include/dvae_hip.h
+ABI_VERSION = 319    # DVAE_ABI_VERSION of include/dvae_hip.h
 
 # name -> (restype, argtypes); mirrors include/dvae_hip.h one to one
 SIGNATURES = {
@@ -141,6 +141,10 @@ SIGNATURES = {
     "dvae_mel_to_windows": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
     "dvae_window_latents": (i32, [vp, vp, vp, vp, vp, C.c_double, vp, i32, i32, i32, i32, vp]),
     "dvae_windows_overlap_add": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, f32, i32, vp]),
+    "dvae_mel_gv": (i32, [vp, i64, vp, i32, i32, vp, vp]),
+    "dvae_modspec_windows": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "dvae_modspec_group_sum": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp]),
+    "dvae_modspec_filter": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp]),
     "dvae_set_compute_mode": (i32, [i32]),
     "dvae_get_compute_mode": (i32, []),
     "dvae_set_deterministic": (i32, [i32]),

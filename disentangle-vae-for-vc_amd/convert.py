@@ -293,13 +293,28 @@ class Converter:
                              f"has T={self.T}, S={self.S}")
 
     # ---- conversion
-    def convert(self, sources: Sequence, targets, bank: StyleBank = None, style_mix: float = 1.0, recons: bool = False) -> list:
+    # ---- over-smoothing (modspec.py)
+    def smoothing_stats(self, targets_by_name: dict, bank: StyleBank, modspec=None) -> tuple:
+        """{name: [mel [80, L], ...]} of the bank's groups -> (natural, generated), two ModSpecStats: the natural statistics of
+        the target mels, and those of the same files converted to their own group's style, self.convert(mels, name,
+        bank)["converted"] — the model's smoothing response on that speaker.  modspec: a ModSpec (default: D = 64)."""
+        from .modspec import ModSpec
+        ms = ModSpec(self.device) if modspec is None else modspec
+        one = lambda g: [g] if (torch.is_tensor(g) or isinstance(g, np.ndarray)) and g.ndim == 2 else list(g)
+        groups = {name: one(g) for name, g in targets_by_name.items()}
+        generated = {name: [r["converted"] for r in self.convert(g, name, bank)] for name, g in groups.items()}
+        return ms.stats(groups), ms.stats(generated)
+
+    def convert(self, sources: Sequence, targets, bank: StyleBank = None, style_mix: float = 1.0, recons: bool = False,
+                postfilter=None) -> list:
         """sources: list of [80, L] arrays / tensors.  With a `bank`, targets is one of its names or one name per source;
         without one, targets is a mel or a list of mels that form the one style group of this call.
         -> per source {"converted": [80, L]} — content of the source, style (1 - style_mix) x the source's own mean style +
         style_mix x the target group's, post-net applied, clamped to [0, 1], exactly L frames.  recons=True adds "recons"
         [80, L] (the source's own mean style, no post-net, no clamp: convert_mel's other decode) and "decoded" (the converted
-        path before the post-net and the clamp)."""
+        path before the post-net and the clamp).  postfilter: None, or (modspec, natural, generated, alpha[, max_gain_db]) — a
+        ModSpec, the two ModSpecStats of `smoothing_stats` and a strength in [0, 1]: "converted" then goes, after the clamp,
+        through modspec.postfilter with the statistics of its source's target name, and is clamped again by the overlap-add."""
         mix = float(style_mix)
         if not 0.0 <= mix <= 1.0:
             raise ValueError(f"convert: style_mix={style_mix} outside [0, 1]")
@@ -336,6 +351,13 @@ class Converter:
                 z0 = window_latents(content, sums, counts, g_src, g_src, 0.0, self.S, counts_host)
                 outs["recons"] = windows_overlap_add(self.decode(z0)[0], utt_d, win_d, self.window, plan["ld"])
             res = [{k: v[:, col0:col0 + L].contiguous() for k, v in outs.items()} for col0, L, _, _ in plan["utt"]]
+            if postfilter is not None:
+                ms, natural, generated, alpha = postfilter[:4]
+                for name in dict.fromkeys(names):
+                    idx = [i for i, n in enumerate(names) if n == name]
+                    for i, y in zip(idx, ms.postfilter([res[i]["converted"] for i in idx], (natural, name), (generated, name),
+                                                       alpha, *postfilter[4:])):
+                        res[i]["converted"] = y
         self.trainer._check_device_errors()
         return res
 
@@ -425,6 +447,12 @@ def _parse(argv):
     p.add_argument("--use-best", action="store_true", default=False, help="voice the checkpoint checkpoints/best.json names")
     p.add_argument("--batch", type=int, default=32, help="windows per forward (one fixed shape)")
     p.add_argument("--seed", type=int, default=1, help="seed of the Griffin-Lim start phase")
+    p.add_argument("--ms-postfilter", type=float, default=None, metavar="ALPHA",
+                   help="modulation-spectrum postfilter of strength ALPHA in (0, 1] against over-smoothing: statistics from the "
+                        "--target files and from their own conversions (off by default)")
+    p.add_argument("--ms-window", type=int, default=64, metavar="D", help="frames per postfilter window (even, 8 ... 128)")
+    p.add_argument("--ms-max-gain-db", type=float, default=12.0, metavar="G",
+                   help="largest gain or attenuation of a modulation component (a safeguard, not a measured optimum)")
     return p.parse_args(argv)
 
 
@@ -437,6 +465,19 @@ def main(argv=None) -> int:
     if not 0.0 <= args.style_mix <= 1.0:
         report(f"--style-mix {args.style_mix} outside [0, 1]")
         return 2
+    if args.ms_postfilter is not None:
+        from .modspec import check_window
+        if not 0.0 < args.ms_postfilter <= 1.0:
+            report(f"--ms-postfilter {args.ms_postfilter} outside (0, 1]")
+            return 2
+        if not args.ms_max_gain_db > 0.0:
+            report(f"--ms-max-gain-db {args.ms_max_gain_db} must be positive")
+            return 2
+        try:
+            check_window(args.ms_window)
+        except ValueError as e:
+            report(f"--ms-window: {e}")
+            return 2
     if not torch.cuda.is_available():
         report("no GPU: conversion runs on the HIP path only")
         return 2
@@ -467,7 +508,16 @@ def main(argv=None) -> int:
     out_dir = args.out or args.log_dir.joinpath("generation", "wav")
     out_dir.mkdir(parents=True, exist_ok=True)
     bank = conv.style_bank({"target": [t[1] for t in targets]})
-    res = conv.convert([s[1] for s in sources], "target", bank, style_mix=args.style_mix)
+    postfilter = None
+    if args.ms_postfilter is not None:
+        from .modspec import ModSpec
+        ms = ModSpec(device, args.ms_window)
+        natural, generated = conv.smoothing_stats({"target": [t[1] for t in targets]}, bank, ms)
+        if natural.windows[0] < 1:
+            report(f"--ms-postfilter: no --target file has {ms.D} frames: no statistics to filter towards")
+            return 1
+        postfilter = (ms, natural, generated, args.ms_postfilter, args.ms_max_gain_db)
+    res = conv.convert([s[1] for s in sources], "target", bank, style_mix=args.style_mix, postfilter=postfilter)
     gen = torch.Generator(device=device)
     gen.manual_seed(args.seed)
     wavs = inv.waveform_batch([r["converted"] for r in res], n_iter=args.griffin_lim_iters, generator=gen)

@@ -1429,3 +1429,6 @@ DVAE_API int dvae_conv_unpack_add_w(const float* dWp, float* dW, int Cout, int C
   hipLaunchKernelGGL(conv_unpack_add_kernel, dim3(nblk(cc)), dim3(256), 0, (hipStream_t)stream, dWp, dW, cc);
   return dvae_check_launch();
 }
+
+// ---- global variance, modulation spectrum and its postfilter: the kernels of modspec.hip, part of this translation unit
+#include "modspec.hip"

@@ -45,7 +45,7 @@ extern "C" {
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below) */
-#define DVAE_ABI_VERSION 318
+#define DVAE_ABI_VERSION 319
 int dvae_version(void);
 
 /* ---- arithmetic of a contraction (every GEMM / conv / LSTM entry point takes a `mode` argument):
@@ -521,6 +521,43 @@ int dvae_window_latents(const float* content, const double* sums, const int64_t*
                         double mix, float* z, int nwin, int S, int Cn, int K, void* stream);
 int dvae_windows_overlap_add(const float* y, const int* utt_table, const int* win_table, const float* w, float* out,
                              int64_t ld, int nutt, int C, int T, float lo, float hi, int clamp, void* stream);
+
+/* ---- over-smoothing of conversions: global variance, modulation spectrum and its postfilter (the
+ * reference has no counterpart).  Mels lie packed as for the window kernels above: x [C, ld], utt_table[nutt][4] = {col0, L,
+ * win0, nwin}.  Windows [nwin][C][D] are what dvae_mel_to_windows cuts with T = D; D even, DVAE_MODSPEC_DMIN <= D <=
+ * DVAE_MODSPEC_DMAX.  twiddle [D][2] float64 = {cos, sin}(2 pi j / D), a host table (dvae_amd.modspec.twiddle).
+ * dvae_mel_gv: out[u][c] = {m, v}, float64: m the mean and v the population variance (divisor L) of x[c][col0 .. col0 + L), two
+ *   passes, the mean first and the centred squares second; a wave per (u, c), lane l adds frames l, l + 64, ... in index order,
+ *   then a fixed tree over the wave: partition and order depend on L alone.  An entry with L < 1 or outside [0, ld) gives NaN
+ *   and reads nothing.
+ * dvae_modspec_windows: per window w and bin c, d_t = y_t - mean_t(y) (no taper), Y_k = sum_t d_t e^{-2 pi i k t / D} for k = 1 ..
+ *   D/2, the sums over t in float64 in index order, s_k = ln max(|Y_k|^2, DVAE_MODSPEC_FLOOR), rounded once to fp32 at the store.
+ *   rows[w C + c] = s_1 .. s_{D/2} | s_1^2 .. s_{D/2}^2 (fp32, D columns; the squares are those of the stored values, taken in
+ *   float64 and rounded once).  k = 0 is zero by construction and is nowhere.  A padding window (all zeros) gives rows of ln
+ *   FLOOR: the reduction passes over them because no group lists them.
+ * dvae_modspec_group_sum: sums[g][c][j] (float64, [G][C][D], overwritten) = the sum of rows[order[i] C + c][j] over i in
+ *   [group_first[g], group_first[g + 1]), in that order starting from +0: in every bit the sequential float64 sum.  order
+ *   [norder] int32 lists window indices group by group, group_first [G + 1] int32; an index outside [0, nwin) is passed over.
+ *   Workgroup (g, c), thread j; only a group's own rows are read.
+ * dvae_modspec_filter: mu_n, sigma_n (natural) and mu_g, sigma_g (generated), float64 [C][D/2]; a sigma below
+ *   DVAE_MODSPEC_SIGMA_MIN counts as that.  Per window, bin and k >= 1:  s' = (1 - alpha) s + alpha (sigma_n / sigma_g (s - mu_g) +
+ *   mu_n);  log-gain = (s' - s) / 2 clamped to +- max_gain_db ln 10 / 20;  Y'_k = Y_k exp(log-gain), the phase kept;  out_t = mean +
+ *   (1 / D) sum_k c_k Re(Y'_k e^{2 pi i k t / D}), k in index order, c_k = 2, c_{D/2} = 1.  All float64, rounded once to fp32.
+ *   alpha = 0 copies the input's bits.  out != windows.
+ * One workgroup per window and tile of 16 bins; frames and twiddles staged once in LDS; no atomics: two launches give the same
+ * bits.  Null pointers, sizes < 1, C > 65535, an odd or out-of-range D, alpha outside [0, 1], max_gain_db <= 0 or a float64
+ * buffer that is not 8-byte aligned return DVAE_EINVAL and launch nothing. */
+#define DVAE_MODSPEC_DMIN 8
+#define DVAE_MODSPEC_DMAX 128
+#define DVAE_MODSPEC_FLOOR 1e-30
+#define DVAE_MODSPEC_SIGMA_MIN 1e-6
+int dvae_mel_gv(const float* x, int64_t ld, const int* utt_table, int nutt, int C, double* out, void* stream);
+int dvae_modspec_windows(const float* windows, int nwin, int C, int D, const double* twiddle, float* rows, void* stream);
+int dvae_modspec_group_sum(const float* rows, const int* order, int norder, const int* group_first, int G, int nwin, int C,
+                           int D, double* sums, void* stream);
+int dvae_modspec_filter(const float* windows, int nwin, int C, int D, const double* twiddle, const double* mu_n,
+                        const double* sigma_n, const double* mu_g, const double* sigma_g, double alpha, double max_gain_db,
+                        float* out, void* stream);
 
 /* ---- mel front-end: preprocessing/utils.py:68-73 `melspectrogram` = lws STFT (1024/256, "speech" window)
  * -> |.| -> 80-mel projection (librosa.filters.mel) -> dB (:127-129) - ref_level_db -> normalise to [0,1] (:136-137).
