@@ -175,6 +175,8 @@ SIGNATURES = {
     "dvae_gmm_ws_bytes": (C.c_size_t, [i64, i32, i32]),
     "dvae_gmm_estep": (i32, [vp, i64, i32, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "dvae_gmm_score": (i32, [vp, i64, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp]),
+    "dvae_latent_tables": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i64, vp]),
+    "dvae_latent_lse": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, vp, i64, vp]),
     "dvae_pair_metrics": (i32, [vp] * 9 + [i32, i64, i32, i32, f32, f32, vp]),
     "dvae_group_sum_f64": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "dvae_prof_enable": (i32, [i32]),

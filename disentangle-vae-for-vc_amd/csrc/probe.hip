@@ -455,3 +455,5 @@ DVAE_API int dvae_gmm_score(const float* x, int64_t ldx, int col0, int D, const 
                      col0, D, segs, a, mu, prec, K, M, out);
   return dvae_check_launch();
 }
+
+#include "latents.hip"      // the latent report: part of this translation unit

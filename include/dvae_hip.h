@@ -44,7 +44,9 @@ extern "C" {
 #define DVAE_EPI_ATOMIC 2 /* C += result with global_atomic_add_f32 (split-K allowed) */
 
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
- * refuses anything else: a stale .so would misread the argument lists below) */
+ * refuses anything else: a stale .so would misread the argument lists below).  The latent report's two entry points
+ * (dvae_latent_tables, dvae_latent_lse) were added at 319 without a new revision: the change is purely additive, no
+ * existing argument list, structure or constant moved. */
 #define DVAE_ABI_VERSION 319
 int dvae_version(void);
 
@@ -788,6 +790,36 @@ int dvae_gmm_estep(const float* x, int64_t ldx, int col0, int64_t N, int D, cons
                    const float* prec, int K, float* lse, float* gamma, void* ws, double* stats, void* stream);
 int dvae_gmm_score(const float* x, int64_t ldx, int col0, int D, const int64_t* segs, int nseg, const float* a,
                    const float* mu, const float* prec, int K, int M, double* out, void* stream);
+
+/* ---- latent report: pairwise posterior log-densities and their log-sum-exps (python -m dvae_amd.latents) ----
+ * Replaces nothing of the reference (its only latent diagnostic is compute_KL_delta_VAE, model/disentangled_vae.py:333-345,
+ * unused): the minibatch-weighted-sampling decomposition of Chen et al. (2018) taken over a whole corpus of N posteriors
+ * N(mu_j, exp lv_j) with one sample z_i each.  Four fp32 tables [N, D] with leading dimension ld; as rounded they ARE the
+ * model:
+ *   z = mu + exp(lv / 2) eps,  a = -(ln 2 pi + lv) / 2,  h = exp(-lv) / 2
+ * dvae_latent_tables: elementwise, mu, lv, eps -> z, a, h (expf of the device library; z by one fma; a by one addition to the
+ *   fp32 constant ln(2 pi) / 2; the halvings are exact).  Columns D .. ld - 1 are neither read nor written.  N = 0: no-op.
+ * dvae_latent_lse: t_ijd = a_jd - h_jd (z_id - mu_jd)^2 (dz = z - mu, q = dz dz, t = fma(-h, q, a)); style_ij = the sum of
+ *   t_ijd over d < S, content_ij over S <= d < D (d ascending from +0, an empty block is 0), joint_ij = style_ij + content_ij.
+ *   jobs [njobs][5] int64 {row0, nrows, col0, ncols, out0} (device, 8-byte aligned; jobs_host the same table on the host, read
+ *   during the call): job k writes, for r < nrows, out[(out0 + r) ldo + c] = the log-sum-exp over j in [col0, col0 + ncols)
+ *   of t_(row0 + r) j c for c < D, of style, content and joint at c = D, D + 1, D + 2; nothing else of out is written.
+ *   A log-sum-exp is m + ln s, (m, s) the running maximum and the sum of exp(. - m): every column takes the maximum off
+ *   before its exponential (e = exp(min(m, t) - max(m, t)); s = t > m ? s e + 1 : s + e, from (-inf, 0)), so a row however
+ *   far from every column gives finite values.  A wave owns 64 rows, one per lane; the four waves of a workgroup take the
+ *   quarters [w q, (w + 1) q), q = ceil(ncols / 4), of the job's columns in ascending order and are merged in wave order
+ *   (m = max(m, m'); s = fma(s', exp(m' - m), s exp(m_old - m)), the earlier waves' pair primed); exponentials are
+ *   v_exp_f32 of the argument times log2 e, the final logarithm is logf.  The partition is a function of (ncols, D) alone, a
+ *   row's bits depend on nothing but its own row of z, the job's columns, D and S — not on the other rows or jobs of the
+ *   launch — and there are no atomics: two launches give the same bits.  Rows and columns must lie inside the tables (the
+ *   entry point does not know N).  A job with nrows = 0 writes nothing; a launch of such jobs only is a no-op.
+ * Null pointers, D < 1, D > DVAE_LATENT_MAX_D, S < 0, S > D, ld < D, ldo < D + 3, njobs < 1, a misaligned jobs, or a job with
+ *   a negative field or ncols < 1 return DVAE_EINVAL and launch nothing. */
+#define DVAE_LATENT_MAX_D 64
+int dvae_latent_tables(const float* mu, const float* lv, const float* eps, float* z, float* a, float* h, int64_t N, int D,
+                       int64_t ld, void* stream);
+int dvae_latent_lse(const float* z, const float* mu, const float* a, const float* h, int64_t ld, int D, int S,
+                    const int64_t* jobs, const int64_t* jobs_host, int njobs, float* out, int64_t ldo, void* stream);
 
 /* ---- held-out validation (model/variational_base_vae.py: validate) ----
  * The reference's test() (variational_base_vae.py:105-123) sums loss_functionGVAE2 (disentangled_vae.py:310-327) over the
