@@ -53,6 +53,13 @@ class LossDesc(C.Structure):
                 ("mse_cof", f32), ("kl_cof", f32)]
 
 
+class LossSched(C.Structure):
+    """dvae_loss_sched_t"""
+    _fields_ = [("coef", vp), ("free_bits", vp), ("D", i32)]
+
+
+LOSS_MAX_D = 1024         # DVAE_LOSS_MAX_D
+
 REPACK_CONV_T, REPACK_LSTM_PACK, REPACK_TRANSPOSE, REPACK_ADD2, REPACK_CAST_BF16, REPACK_COPY_F32 = 0, 1, 2, 3, 4, 5
 
 # DVAE_MODE_* of include/dvae_hip.h
@@ -103,6 +110,8 @@ SIGNATURES = {
     "dvae_loss_ws_bytes": (i64, [i64]),
     "dvae_loss_fwd": (i32, [C.POINTER(LossDesc), vp, vp, vp]),
     "dvae_loss_bwd": (i32, [C.POINTER(LossDesc), vp] + [vp] * 10 + [vp]),
+    "dvae_loss_fwd_sched": (i32, [C.POINTER(LossDesc), C.POINTER(LossSched), vp, vp, vp, vp]),
+    "dvae_loss_bwd_sched": (i32, [C.POINTER(LossDesc), C.POINTER(LossSched), vp, vp] + [vp] * 10 + [vp]),
     "dvae_gemm_f32_batched": (i32, [vp, vp, vp, i32, i32, i32, i32, i64, i64, i64, i32, i32, i32, i32, i32, vp]),
     "dvae_gemm_f32_slabs": (i32, [vp, vp, vp, vp, i64, i32, vp, i32, i32, i32, i64, i64, i64, i32, i32, i32, i32, i32, vp]),
     "dvae_gemm_f32_batched_slabs": (i32, [vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, i64, i64, i64, i32, i32, i32, i32,

@@ -182,9 +182,21 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(const LossArgs a, dou
     part[blockIdx.x * 4 + threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
 }
 
+// The scheduled form of the two kernels below (dvae_loss_fwd_sched / dvae_loss_bwd_sched): the two weights are read from
+// device memory, so a captured step follows a KL warm-up without a new capture, and each latent dimension may spend
+// free_bits[j] nats unpenalised.  SCHED = false is dvae_loss_fwd / dvae_loss_bwd: `s` is not looked at.
+struct LossSched {
+  const float* coef;        // [8]: [0] mse_cof, [1] the KL weight in effect
+  const float* free_bits;   // [D] or null
+  float* aux;               // [4 + 4 D], see include/dvae_hip.h (read-only in the backward kernel)
+  int D;
+};
+constexpr int LOSS_MAX_D = DVAE_LOSS_MAX_D;
+
 // out[8] = (LOSS, L1_x1, L1_x2, L1_x1hat, L1_x2hat, KL_z1, KL_z2, KL_style)
+template <bool SCHED>
 __global__ __launch_bounds__(256) void loss_final_kernel(const LossArgs a, const double* __restrict__ part, int nparts,
-                                                         float* __restrict__ out) {
+                                                         float* __restrict__ out, const LossSched s) {
   __shared__ double red[7][4];
   double v[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (int i = threadIdx.x; i < nparts; i += 256)
@@ -196,12 +208,47 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const LossArgs a, const
     v[5] += kl(a.qmu[1][i], a.qlv[1][i]);
   }
   for (int i = threadIdx.x; i < a.ns; i += 256) v[6] += kl(a.smu[i], a.slv[i]);
+  // per-dimension batch-mean KL of the [rows, D] blocks: a thread owns a column and adds its rows in row order in float64
+  // (consecutive threads read consecutive addresses), one rounding at the store; the order depends on the shapes alone
+  __shared__ float kd[SCHED ? 2 * LOSS_MAX_D : 1];
+  __shared__ float clamped[2];
+  if constexpr (SCHED) {
+    const int rows = a.nq / s.D;
+    for (int j = threadIdx.x; j < s.D; j += 256)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        double c = 0.0;
+        for (int i = 0; i < rows; ++i) c += kl(a.qmu[k][i * s.D + j], a.qlv[k][i * s.D + j]);
+        const float m = (float)(c * (double)a.kl_scale);
+        kd[k * LOSS_MAX_D + j] = m;
+        s.aux[4 + k * s.D + j] = m;
+        s.aux[4 + (2 + k) * s.D + j] = (!s.free_bits || m > s.free_bits[j]) ? 1.f : 0.f;     // the gate is strict
+      }
+  }
 #pragma unroll
   for (int k = 0; k < 7; ++k) {
     const double d = wave_sum_d(v[k]);
     if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = d;
   }
   __syncthreads();
+  if constexpr (SCHED) {
+    if (s.free_bits) {      // sum_j max(lambda_j, kl_dim[j]) in float64 in dimension order: one lane per half
+      if ((threadIdx.x & 63) == 0 && threadIdx.x < 128) {
+        const int k = threadIdx.x >> 6;
+        double c = 0.0;
+        int nfree = 0;
+        for (int j = 0; j < s.D; ++j) {
+          const float m = kd[k * LOSS_MAX_D + j], lam = s.free_bits[j];
+          const bool on = m > lam;
+          c += (double)(on ? m : lam);
+          nfree += on ? 0 : 1;
+        }
+        clamped[k] = (float)c;
+        s.aux[2 + k] = (float)nfree;
+      }
+      __syncthreads();
+    }
+  }
   if (threadIdx.x == 0) {
     float t[7];
 #pragma unroll
@@ -211,23 +258,36 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const LossArgs a, const
       out[1 + k] = t[k];
     }
     // the reference's operation order: mse_cof * (((a + b) + c) + d) + kl_cof * (e + f), all in fp32
-    out[0] = a.mse_cof * (((t[0] + t[1]) + t[2]) + t[3]) + a.kl_cof * (t[4] + t[5]);
+    if constexpr (SCHED) {
+      // out[1..7] stay the raw terms; what enters LOSS is aux[0..1]: the terms themselves, or the clamped sums
+      const float e = s.free_bits ? clamped[0] : t[4], f = s.free_bits ? clamped[1] : t[5];
+      s.aux[0] = e;
+      s.aux[1] = f;
+      if (!s.free_bits) s.aux[2] = s.aux[3] = 0.f;
+      // spelled out as the compiler contracts the expression of the other branch (one product, then one fused
+      // multiply-add): with both weights in registers it would pair the two products and add, which rounds differently
+      out[0] = __builtin_fmaf(s.coef[1], e + f, s.coef[0] * (((t[0] + t[1]) + t[2]) + t[3]));
+    } else {
+      out[0] = a.mse_cof * (((t[0] + t[1]) + t[2]) + t[3]) + a.kl_cof * (t[4] + t[5]);
+    }
   }
 }
 
 // gradients w.r.t. the four reconstructions and the six latent statistics, given g[8] = dL/d(out[8])
+template <bool SCHED>
 __global__ __launch_bounds__(256) void loss_bwd_kernel(const LossArgs a, const float* __restrict__ g, float* __restrict__ dr0,
                                                        float* __restrict__ dr1, float* __restrict__ dr2,
                                                        float* __restrict__ dr3, float* __restrict__ dqmu0,
                                                        float* __restrict__ dqlv0, float* __restrict__ dqmu1,
                                                        float* __restrict__ dqlv1, float* __restrict__ dsmu,
-                                                       float* __restrict__ dslv, int l1_blocks) {
+                                                       float* __restrict__ dslv, int l1_blocks, const LossSched s) {
   const float g0 = g[0];
+  const float mse_cof = SCHED ? s.coef[0] : a.mse_cof, kl_cof = SCHED ? s.coef[1] : a.kl_cof;
   if ((int)blockIdx.x < l1_blocks) {
     float* dr[4] = {dr0, dr1, dr2, dr3};
     float w[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] = (g0 * a.mse_cof + g[1 + k]) * a.l1_scale;
+    for (int k = 0; k < 4; ++k) w[k] = (g0 * mse_cof + g[1 + k]) * a.l1_scale;
     const int64_t n4 = a.n >> 2;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)l1_blocks * 256) {
       const f32x4 x1 = *reinterpret_cast<const f32x4*>(a.x[0] + 4 * i), x2 = *reinterpret_cast<const f32x4*>(a.x[1] + 4 * i);
@@ -256,10 +316,23 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const LossArgs a, const f
     return;
   }
   // latent statistics: one extra workgroup
-  const float w1 = (g0 * a.kl_cof + g[5]) * a.kl_scale, w2 = (g0 * a.kl_cof + g[6]) * a.kl_scale, ws = g[7] * a.style_scale;
-  for (int i = threadIdx.x; i < a.nq; i += 256) {
-    if (dqmu0) { dqmu0[i] = w1 * (-2.f * a.qmu[0][i]); dqlv0[i] = w1 * (1.f - expf(a.qlv[0][i])); }
-    if (dqmu1) { dqmu1[i] = w2 * (-2.f * a.qmu[1][i]); dqlv1[i] = w2 * (1.f - expf(a.qlv[1][i])); }
+  const float w1 = (g0 * kl_cof + g[5]) * a.kl_scale, w2 = (g0 * kl_cof + g[6]) * a.kl_scale, ws = g[7] * a.style_scale;
+  if (SCHED && s.free_bits) {
+    // a free dimension (gate 0) takes nothing from g[0]: what is left of its weight is the direct gradient of out[5 + k];
+    // a penalised one has the weight of the ungated kernel, bit for bit
+    const float f1 = g[5] * a.kl_scale, f2 = g[6] * a.kl_scale;
+    const float* gate = s.aux + 4 + 2 * s.D;
+    for (int i = threadIdx.x; i < a.nq; i += 256) {
+      const int j = i % s.D;
+      const float u1 = gate[j] != 0.f ? w1 : f1, u2 = gate[s.D + j] != 0.f ? w2 : f2;
+      if (dqmu0) { dqmu0[i] = u1 * (-2.f * a.qmu[0][i]); dqlv0[i] = u1 * (1.f - expf(a.qlv[0][i])); }
+      if (dqmu1) { dqmu1[i] = u2 * (-2.f * a.qmu[1][i]); dqlv1[i] = u2 * (1.f - expf(a.qlv[1][i])); }
+    }
+  } else {
+    for (int i = threadIdx.x; i < a.nq; i += 256) {
+      if (dqmu0) { dqmu0[i] = w1 * (-2.f * a.qmu[0][i]); dqlv0[i] = w1 * (1.f - expf(a.qlv[0][i])); }
+      if (dqmu1) { dqmu1[i] = w2 * (-2.f * a.qmu[1][i]); dqlv1[i] = w2 * (1.f - expf(a.qlv[1][i])); }
+    }
   }
   if (dsmu)
     for (int i = threadIdx.x; i < a.ns; i += 256) {
@@ -948,7 +1021,7 @@ DVAE_API int dvae_loss_fwd(const dvae_loss_desc_t* desc, float* out8, void* ws, 
   hipStream_t s = (hipStream_t)stream;
   const int blocks = nblk(a.n / 4 + 1, 256, L1_BLOCKS);
   hipLaunchKernelGGL(loss_partial_kernel, dim3(blocks), dim3(256), 0, s, a, (double*)ws);
-  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, a, (const double*)ws, blocks, out8);
+  hipLaunchKernelGGL(loss_final_kernel<false>, dim3(1), dim3(256), 0, s, a, (const double*)ws, blocks, out8, LossSched{});
   return dvae_check_launch();
 }
 
@@ -963,8 +1036,53 @@ DVAE_API int dvae_loss_bwd(const dvae_loss_desc_t* desc, const float* g8, float*
   for (const float* p : outs)
     if (p && (((uintptr_t)p) & 15)) return DVAE_EINVAL;
   const int blocks = nblk(a.n / 4 + 1, 256, 1024);
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(blocks + 1), dim3(256), 0, (hipStream_t)stream, a, g8, d_recon1, d_recon2,
-                     d_recon1_hat, d_recon2_hat, d_q1_mu, d_q1_lv, d_q2_mu, d_q2_lv, d_s_mu, d_s_lv, blocks);
+  hipLaunchKernelGGL(loss_bwd_kernel<false>, dim3(blocks + 1), dim3(256), 0, (hipStream_t)stream, a, g8, d_recon1, d_recon2,
+                     d_recon1_hat, d_recon2_hat, d_q1_mu, d_q1_lv, d_q2_mu, d_q2_lv, d_s_mu, d_s_lv, blocks, LossSched{});
+  return dvae_check_launch();
+}
+
+namespace {
+// the weights and the free bits of a scheduled call: null coef / aux, D out of range or not dividing nq, misaligned
+int fill_loss_sched(LossSched& s, const LossArgs& a, const dvae_loss_sched_t* sc, const float* aux) {
+  if (!sc || !sc->coef || !aux) return DVAE_EINVAL;
+  if (sc->D < 1 || sc->D > DVAE_LOSS_MAX_D || a.nq % sc->D != 0) return DVAE_EINVAL;
+  if ((((uintptr_t)sc->coef) | ((uintptr_t)aux) | ((uintptr_t)sc->free_bits)) & 3) return DVAE_EINVAL;
+  s.coef = sc->coef; s.free_bits = sc->free_bits; s.aux = const_cast<float*>(aux); s.D = sc->D;
+  return DVAE_OK;
+}
+}  // namespace
+
+DVAE_API int dvae_loss_fwd_sched(const dvae_loss_desc_t* desc, const dvae_loss_sched_t* sched, float* out8, float* aux,
+                                 void* ws, void* stream) {
+  LossArgs a;
+  LossSched sc;
+  int rc = fill_loss_args(a, desc);
+  if (rc) return rc;
+  if (!out8 || !ws) return DVAE_EINVAL;
+  if ((rc = fill_loss_sched(sc, a, sched, aux))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int blocks = nblk(a.n / 4 + 1, 256, L1_BLOCKS);
+  hipLaunchKernelGGL(loss_partial_kernel, dim3(blocks), dim3(256), 0, s, a, (double*)ws);
+  hipLaunchKernelGGL(loss_final_kernel<true>, dim3(1), dim3(256), 0, s, a, (const double*)ws, blocks, out8, sc);
+  return dvae_check_launch();
+}
+
+DVAE_API int dvae_loss_bwd_sched(const dvae_loss_desc_t* desc, const dvae_loss_sched_t* sched, const float* aux,
+                                 const float* g8, float* d_recon1, float* d_recon2, float* d_recon1_hat,
+                                 float* d_recon2_hat, float* d_q1_mu, float* d_q1_lv, float* d_q2_mu, float* d_q2_lv,
+                                 float* d_s_mu, float* d_s_lv, void* stream) {
+  LossArgs a;
+  LossSched sc;
+  int rc = fill_loss_args(a, desc);
+  if (rc) return rc;
+  if (!g8 || (!d_q1_mu != !d_q1_lv) || (!d_q2_mu != !d_q2_lv) || (!d_s_mu != !d_s_lv)) return DVAE_EINVAL;
+  const float* outs[] = {d_recon1, d_recon2, d_recon1_hat, d_recon2_hat};
+  for (const float* p : outs)
+    if (p && (((uintptr_t)p) & 15)) return DVAE_EINVAL;
+  if ((rc = fill_loss_sched(sc, a, sched, aux))) return rc;
+  const int blocks = nblk(a.n / 4 + 1, 256, 1024);
+  hipLaunchKernelGGL(loss_bwd_kernel<true>, dim3(blocks + 1), dim3(256), 0, (hipStream_t)stream, a, g8, d_recon1, d_recon2,
+                     d_recon1_hat, d_recon2_hat, d_q1_mu, d_q1_lv, d_q2_mu, d_q2_lv, d_s_mu, d_s_lv, blocks, sc);
   return dvae_check_launch();
 }
 

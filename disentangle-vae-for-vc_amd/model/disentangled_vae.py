@@ -29,7 +29,7 @@ from typing import Optional, Sequence
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
 from ..ops import (ACT_NONE, fanout, ACT_RELU, ACT_TANH, ConvBnActFn, FramesToMelFn, LatentFn, LinearFn, LstmLayerFn,
                    LstmStack2Fn, Permute102Fn, mel_frames, mel_to_frames)
 from ..derived import DerivedWeights
@@ -513,9 +513,64 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         return self.losses_vector(x1, x2, x_recon1, x_recon2, recons_x1_hat, recons_x2_hat, q_z1_mu, q_z1_logvar,
                                   q_z2_mu, q_z2_logvar, style_mu1, style_logvar1).unbind(0)
 
+    def set_kl_schedule(self, kind=None, *, start=0.0, steps=0, cycles=4, ratio=0.5, free_bits=None):
+        """KL annealing and per-dimension free bits on the TRAINING step, inside the replayed graph (kl_schedule.py has the
+        definitions).  kind: None (off: the step launches what it launched without this), "constant"
+        (the weight is `kl_cof`), "linear" (from `start` to `kl_cof` over `steps` optimiser steps, then hold), "cyclical"
+        (`steps` cut into `cycles` cycles, each ramping over its first `ratio`), "double" (the reference's update_kl():
+        `start`, doubled once per epoch, capped at `kl_cof`).  free_bits: None, one float, a (style, content) pair or one
+        value per latent dimension, in nats: a dimension whose batch-mean KL is not ABOVE its value is not penalised.
+        The weight lives in a device buffer the loss kernels read (ops.LossGVAE2SchedFn): changing it costs one small copy
+        before the step and never a new capture; switching the feature or the free bits on or off changes the launches'
+        arguments and captures again.  The position of the schedule is the optimiser's step count, so a resumed run
+        continues it, and a step Adam skips does not advance it (the host's count is set right from `FlatAdam.t` whenever
+        the host reads the device anyway: in `step`, and at the end of an epoch of `train`).
+        ONLY the training loss changes: `loss_functionGVAE2`, `losses_vector`, `step(train=False)`, `validate` and
+        ops.pair_metrics keep the configured `kl_cof` and no free bits, so `Val/Loss` and checkpoints/best.json compare
+        epochs under one fixed objective.  Data parallel: every rank computes the same weight from the same step count;
+        free bits gate on each rank's LOCAL minibatch; nothing is exchanged."""
+        from ..kl_schedule import KLSchedule, expand_free_bits
+        opt = self.optimizer
+        if kind is None:
+            if free_bits is not None:
+                raise ValueError("set_kl_schedule: free_bits needs a schedule (\"constant\" keeps the weight at kl_cof)")
+            self.kl_sched = None
+            opt.kl_schedule = None
+            return
+        S, Cn = self.model.speaker_size, self.model.latent_dim - self.model.speaker_size
+        D = S + Cn
+        sched = KLSchedule(kind, start, steps, cycles, ratio, expand_free_bits(free_bits, S, Cn))
+        dev = opt.flat_p.device
+        if dev.type != "cuda":
+            raise RuntimeError("set_kl_schedule: the scheduled loss runs only on the HIP device (no CPU fallback)")
+        if D > _lib.LOSS_MAX_D:
+            raise ValueError(f"set_kl_schedule: {D} latent dimensions, the loss kernels take {_lib.LOSS_MAX_D}")
+        if getattr(self, "_kl_coef", None) is None:     # allocated once: a captured graph holds their addresses
+            self._kl_coef = torch.zeros(8, device=dev, dtype=torch.float32)
+            self.kl_aux = torch.zeros(4 + 4 * D, device=dev, dtype=torch.float32)
+            self._kl_fb = torch.zeros(D, device=dev, dtype=torch.float32)
+            self._kl_pin, self._kl_pin_ev, self._kl_pin_i = None, None, 0
+        if sched.free_bits is not None:
+            self._kl_fb.copy_(torch.tensor(sched.free_bits, dtype=torch.float32))
+        self.kl_sched = sched
+        opt.kl_schedule = sched.params()        # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
+        self._kl_sent, self._kl_k, self.kl_weight = None, None, None
+
+    def kl_weight_at(self, k, epoch=1):
+        """The KL weight of the step that runs after `k` optimiser steps, in epoch `epoch` (kl_schedule.KLSchedule)."""
+        if getattr(self, "kl_sched", None) is None:
+            return float(self.kl_cof)
+        return self.kl_sched.weight_at(k, epoch, self.kl_cof)
+
     def losses_vector_full(self, x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv):
-        """losses_vector on the unsplit outputs of `DisentangledVAE.forward_full` (the training step's path)."""
+        """losses_vector on the unsplit outputs of `DisentangledVAE.forward_full` (the training step's path).  While a KL
+        schedule is on (set_kl_schedule) the weights come from the device and `self.kl_aux` receives the per-dimension KL."""
         inv_b = 1.0 / float(self.batch_size)
+        sched = getattr(self, "kl_sched", None)
+        if sched is not None:
+            return ops.LossGVAE2SchedFn.apply(x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv, inv_b, -0.5 / x1.shape[0], -inv_b,
+                                              self._kl_coef, self._kl_fb if sched.free_bits is not None else None,
+                                              q_mu.shape[1], self.kl_aux)
         return ops.LossGVAE2FullFn.apply(x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv, inv_b, -0.5 / x1.shape[0], -inv_b,
                                          self.mse_cof, self.kl_cof)
 

@@ -109,10 +109,46 @@ class VariationalBaseModelVAE:
     def _graph_signature(self, data1):
         from .. import ops
         opt = self.optimizer
-        return (tuple(data1.shape), tuple(opt.betas), float(opt.eps),
-                float(self.mse_cof), float(self.kl_cof), int(self.batch_size), bool(self.model.training),
+        # with a KL schedule the two weights are read from the device (set_kl_schedule): their values are no part of the graph
+        kl = self._kl_signature()
+        cofs = () if kl else (float(self.mse_cof), float(self.kl_cof))
+        return (tuple(data1.shape), tuple(opt.betas), float(opt.eps)) + cofs + (
+                int(self.batch_size), bool(self.model.training),
                 self.reducer is not None, getattr(self.reducer, "world_size", 1), ops.current_mode(),
-                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature()
+                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature() + kl
+
+    def _kl_signature(self):
+        """A KL schedule on/off, and free bits on/off, change the loss launches of a step; the weight does not (a device
+        scalar, _sync_kl_coef).  Nothing is added while it is off."""
+        sched = getattr(self, "kl_sched", None)
+        return (("kl_sched", sched.free_bits is not None),) if sched is not None else ()
+
+    def _sync_kl_coef(self):
+        """Host -> device copy of (mse_cof, the KL weight of the step about to run) when the pair changed since the last
+        copy; beside optimizer.sync_scalars, never inside a capture.  The step about to run is number `_kl_k` by the host's
+        count, which starts from FlatAdam.t (one read) and is set right from it wherever the host reads the device anyway."""
+        if getattr(self, "kl_sched", None) is None:
+            return
+        if self._kl_k is None:
+            self._kl_k = self.optimizer.t
+        w = self.kl_weight_at(self._kl_k, getattr(self, "_kl_epoch", 1))
+        pair = (float(self.mse_cof), float(w))
+        if pair != self._kl_sent:
+            # staged through a small ring of pinned slots like FlatAdam.sync_scalars: a per-step schedule must not stall the host
+            if self._kl_pin is None:
+                self._kl_pin = torch.empty(16, 2, dtype=torch.float32, pin_memory=True)
+                self._kl_pin_ev = [None] * 16
+            i = self._kl_pin_i = (self._kl_pin_i + 1) % 16
+            if self._kl_pin_ev[i] is not None:
+                self._kl_pin_ev[i].synchronize()
+            self._kl_pin[i, 0], self._kl_pin[i, 1] = pair
+            self._kl_coef[0:2].copy_(self._kl_pin[i], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._kl_pin_ev[i] = ev
+            self._kl_sent = pair
+        self.kl_weight = float(w)
+        self._kl_k += 1         # Adam advances t with this step (or skips it: set right at the next read of t)
 
     def _clip_signature(self):
         """Gradient clipping on/off and the guard change the launches of a step; the VALUE of max_norm does not (a device
@@ -133,9 +169,11 @@ class VariationalBaseModelVAE:
         averages already, and are the same inside and outside."""
         return self.optimizer.ema_weights()
 
-    def _eager_train_step(self, data1, data2):
+    def _eager_train_step(self, data1, data2, kl_sent=False):
         # (until round 5 the step ran inside an ops.ZeroArena: one clear launch for the outputs that split-k contractions
         # accumulated into atomically; split contractions store slabs now and nothing needs clearing)
+        if not kl_sent:                 # _step_graph sends the weights of a KL schedule itself, before capture / replay
+            self._sync_kl_coef()
         return self._train_step_body(data1, data2)
 
     def _train_step_body(self, data1, data2):
@@ -195,6 +233,7 @@ class VariationalBaseModelVAE:
         m.eps_override = self._g_eps
         # learning rate / gradient scale: device scalars, refreshed OUTSIDE the captured region
         self.optimizer.sync_scalars(1.0 / self.reducer.world_size if self.reducer is not None else 1.0)
+        self._sync_kl_coef()            # likewise the loss weights of a KL schedule (nothing while it is off)
         if self._graph is not None and not getattr(self.optimizer, "_clean", True):
             # something accumulated into the gradient buffer since the last Adam launch (a manual backward between two
             # replays): a graph captured on a clean buffer holds no zero_grad launch of its own
@@ -222,7 +261,7 @@ class VariationalBaseModelVAE:
                     _time.sleep(0.5)
                 try:
                     with torch.cuda.graph(g, **mode):
-                        self._g_losses = self._eager_train_step(self._g_x1, self._g_x2)
+                        self._g_losses = self._eager_train_step(self._g_x1, self._g_x2, kl_sent=True)
                 except Exception as e:      # nothing of the step has run: fall back to the eager step, for good
                     if self.reducer is None:
                         raise
@@ -232,7 +271,7 @@ class VariationalBaseModelVAE:
                     self._use_graph = False
                     self._graph = None
                     torch.cuda.synchronize()
-                    return self._eager_train_step(self._g_x1, self._g_x2)
+                    return self._eager_train_step(self._g_x1, self._g_x2, kl_sent=True)
                 self._graph = g
             self._graph.replay()
             if getattr(self.optimizer, "fold_zero_grad", False):
@@ -251,6 +290,12 @@ class VariationalBaseModelVAE:
 
     # ---- variational_base_vae.py:58-70
     def step(self, data1, data2, speaker_ids, train=False):
+        if train and getattr(self, "kl_sched", None) is not None:
+            # the same one copy carries the optimiser's step count: the schedule's position is exactly t (a skipped step)
+            vec = torch.cat([self.step_async(data1, data2, speaker_ids), self.optimizer.dev_state[0:1]]).tolist()
+            self._kl_k = int(vec[8])
+            self._check_and_recover()
+            return tuple(vec[:8])
         if train:
             out = tuple(self.step_async(data1, data2, speaker_ids).tolist())   # one D2H copy, not 8 .item() syncs
             self._check_and_recover()
@@ -295,29 +340,58 @@ class VariationalBaseModelVAE:
             gmax = torch.zeros(1, dtype=torch.float32, device=self.device)
             zero = torch.zeros(1, dtype=torch.float32, device=self.device)
             before = opt.clip_state[5:7].clone()
+        # a KL schedule on (set_kl_schedule): the free counts and the per-dimension KL of every step (kl_aux[2 : 4 + 2 D]) join
+        # a running float64 tensor the same way, and the optimiser's step count rides along to set the schedule's position right
+        sched = getattr(self, "kl_sched", None)
+        self.kl_stats = self.kl_dims = None
+        if sched is not None:
+            self._kl_epoch = max(1, int(epoch))
+            kD = (self.kl_aux.numel() - 4) // 4
+            ksum = torch.zeros(2 + 2 * kD, dtype=torch.float64, device=self.device)
+            ksteps = 0
         for data1, data2, speaker_ids in train_loader:
             data1 = data1.to(self.device, non_blocking=True).float()
             data2 = data2.to(self.device, non_blocking=True).float()
             speaker_ids = speaker_ids.view(-1)
             last = self.step_async(data1, data2, speaker_ids)
             tot.add_(last)
+            if sched is not None:
+                ksum.add_(self.kl_aux[2:4 + 2 * kD])
+                ksteps += 1
             if clip:
                 ok = torch.isfinite(opt.clip_state[1:2])
                 norm = torch.where(ok, opt.clip_state[1:2], zero)
                 gsum.add_(torch.cat([norm, ok.float()]))
                 torch.maximum(gmax, norm, out=gmax)
+        ktail = []
+        if sched is not None:
+            tot = torch.cat([tot, ksum, opt.dev_state[0:1].double()])     # behind the eight sums, in front of the rest
         if clip:
             # the epoch's single copy carries them along
             packed = torch.cat([tot, gsum, gmax.double(), (opt.clip_state[5:7] - before).double()]
                                + ([opt.ema_state[1:3].double()] if ema else [])).tolist()
+            if sched is not None:
+                ktail, packed = packed[8:11 + 2 * kD], packed[:8] + packed[11 + 2 * kD:]
             tot = packed[:8]
             self.grad_stats = {"Grad/Norm mean": packed[8] / max(1.0, packed[9]), "Grad/Norm max": packed[10],
                                "Grad/Skipped steps": int(packed[11]), "Grad/Clipped steps": int(packed[12])}
         elif ema:
             packed = torch.cat([tot, opt.ema_state[1:3].double()]).tolist()
+            if sched is not None:
+                ktail = packed[8:11 + 2 * kD]
             tot = packed[:8]
         else:
             tot = tot.tolist()
+            if sched is not None:
+                ktail, tot = tot[8:], tot[:8]
+        if sched is not None:
+            self._kl_k = int(ktail[-1])
+            n = max(1, ksteps)
+            z1, z2 = [v / n for v in ktail[2:2 + kD]], [v / n for v in ktail[2 + kD:2 + 2 * kD]]
+            self.kl_dims = {"epoch": epoch, "steps": ksteps, "z1": z1, "z2": z2}
+            self.kl_stats = {"KL/Weight": self.kl_weight if self.kl_weight is not None else self.kl_weight_at(self._kl_k, self._kl_epoch),
+                             "KL/Free dims z1": ktail[0] / n, "KL/Free dims z2": ktail[1] / n,
+                             "KL/Active dims": sum(1 for v in z1 if v > 0.01)}
         if ema:
             self.ema_stats = {"EMA/Updates": int(packed[-2]), "EMA/Weight": packed[-1]}
         self._check_and_recover()
@@ -442,6 +516,13 @@ class VariationalBaseModelVAE:
         if os.path.exists(opt):
             sd = torch.load(opt, map_location="cpu")
             self.optimizer.load_state_dict(sd, legacy_layout=os.environ.get("DVAE_OPT_LEGACY_LAYOUT"))
+            # the KL schedule the checkpoint was trained under (load_state_dict has refused a different one): restored when
+            # none was asked for, and continued either way at the step count just loaded
+            saved = sd.get("kl_schedule")
+            if saved is not None and getattr(self, "kl_sched", None) is None and hasattr(self, "set_kl_schedule"):
+                self.set_kl_schedule(saved["kind"], **{k: saved[k] for k in ("start", "steps", "cycles", "ratio", "free_bits")})
+            if getattr(self, "kl_sched", None) is not None:
+                self._kl_k = None
             if sd.get("cuda_rng_state") is not None and torch.device(self.device).type == "cuda":
                 g = torch.cuda.default_generators[torch.device(self.device).index or 0]
                 if self.reducer is not None and self.reducer.rank > 0:
@@ -603,6 +684,12 @@ class VariationalBaseModelVAE:
                 rec.update(self.grad_stats)
             if getattr(self, "ema_stats", None):        # weight average on (FlatAdam.set_ema)
                 rec.update(self.ema_stats)
+            if getattr(self, "kl_stats", None):         # KL schedule on (set_kl_schedule)
+                rec.update(self.kl_stats)
+                if logs_path and self._is_rank0():
+                    # beside the logs directory: <log_dir>/kl_dims.json, this epoch's mean KL per latent dimension in nats
+                    with open(os.path.join(os.path.dirname(os.path.normpath(logs_path)), "kl_dims.json"), "w") as fp:
+                        json.dump(self.kl_dims, fp, indent=1)
             ckpt_epoch = epoch % report_interval == 0 and bool(checkpoints_path)
             val = None
             if val_pairs is not None and self._is_rank0() and (epoch % max(1, int(val_interval)) == 0 or ckpt_epoch):

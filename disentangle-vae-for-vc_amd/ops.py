@@ -1499,6 +1499,63 @@ class LossGVAE2FullFn(torch.autograd.Function):
         return (None, None, *[grads[i] if need[i + 2] else None for i in range(6)], None, None, None, None, None)
 
 
+class LossGVAE2SchedFn(torch.autograd.Function):
+    """LossGVAE2FullFn with the two weights read ON THE DEVICE from `coef` (float[8]: mse_cof, the KL weight in effect) and
+    per-dimension free bits (`free_bits` float[D] nats, or None): dvae_loss_fwd_sched / dvae_loss_bwd_sched.  A captured
+    step then follows a KL schedule without a new capture.  `aux` (float[4 + 4 D]) belongs to the CALLER: the trainer adds
+    it up across steps and a captured graph holds its address; forward fills it (the KL terms as they enter LOSS, the
+    free counts, the per-dimension KL, the gate) and backward reads the gate from it.  Returns the same [8] vector;
+    [1..7] are the raw terms, free bits or not."""
+
+    @staticmethod
+    def _sched(coef, free_bits, D):
+        s = _lib.LossSched()
+        s.coef, s.free_bits, s.D = ptr(coef), ptr(free_bits), int(D)
+        return s
+
+    @staticmethod
+    def forward(ctx, x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv, l1_scale, kl_scale, style_scale, coef, free_bits, D, aux):
+        ts = [t.contiguous() for t in (x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv)]
+        _ok(*ts)
+        if not (ts[0].numel() == ts[1].numel() and ts[2].numel() == ts[3].numel() == 2 * ts[0].numel()):
+            raise ValueError("loss: reconstructions must hold the x1 and the x2 half")
+        if not (ts[4].numel() == ts[5].numel() and ts[4].numel() % 2 == 0 and ts[6].numel() == ts[7].numel()):
+            raise ValueError("loss: mu / logvar shapes do not match")
+        D = int(D)
+        _ok(coef, aux, *([] if free_bits is None else [free_bits]))
+        if not (coef.is_contiguous() and aux.is_contiguous() and coef.numel() >= 8 and aux.numel() >= 4 + 4 * D):
+            raise ValueError("loss: coef is a contiguous float[8], aux a contiguous float[4 + 4 D]")
+        if free_bits is not None and not (free_bits.is_contiguous() and free_bits.numel() == D):
+            raise ValueError("loss: free_bits is a contiguous float[D]")
+        scales = (float(l1_scale), float(kl_scale), float(style_scale), 0.0, 0.0)        # the desc's weights are ignored
+        L = lib()
+        out = torch.empty(8, device=ts[0].device, dtype=torch.float32)
+        ws = torch.empty((L.dvae_loss_ws_bytes(ts[0].numel()),), device=ts[0].device, dtype=torch.uint8)
+        d = LossGVAE2FullFn._desc(*ts, scales)
+        s = LossGVAE2SchedFn._sched(coef, free_bits, D)
+        check(L.dvae_loss_fwd_sched(C.byref(d), C.byref(s), ptr(out), ptr(aux), ptr(ws), stream()), "dvae_loss_fwd_sched")
+        ctx.save_for_backward(*ts, coef, aux, *([] if free_bits is None else [free_bits]))
+        ctx.scales, ctx.D = scales, D
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        ts, coef, aux = saved[:8], saved[8], saved[9]
+        free_bits = saved[10] if len(saved) > 10 else None
+        g = g.contiguous()
+        grads = [torch.empty_like(t) for t in ts[2:]]            # rec, rec_hat, q_mu, q_lv, s_mu, s_lv
+        d = LossGVAE2FullFn._desc(*ts, ctx.scales)
+        s = LossGVAE2SchedFn._sched(coef, free_bits, ctx.D)
+        n, nq = ts[0].numel(), ts[4].numel() // 2
+        gp = lambda t, off=0: t.data_ptr() + 4 * off
+        check(lib().dvae_loss_bwd_sched(C.byref(d), C.byref(s), ptr(aux), ptr(g), gp(grads[0]), gp(grads[0], n), gp(grads[1]),
+                                        gp(grads[1], n), gp(grads[2]), gp(grads[3]), gp(grads[2], nq), gp(grads[3], nq),
+                                        gp(grads[4]), gp(grads[5]), stream()), "dvae_loss_bwd_sched")
+        need = ctx.needs_input_grad
+        return (None, None, *[grads[i] if need[i + 2] else None for i in range(6)], None, None, None, None, None, None, None)
+
+
 # ----------------------------------------------------------------------------- softmax cross-entropy (probe.py)
 CE_MAX_CLASSES = 1024     # DVAE_CE_MAX_CLASSES
 

@@ -93,6 +93,9 @@ class FlatAdam:
         self.ema, self.ema_state = None, None
         self._dev_ema = None               # (decay, warmup) as last written to ema_state[0], [3]
         self.ema_swapped = False           # True: flat_p holds the average and self.ema the weights (swap_ema)
+        # the KL schedule the trainer runs under (ConvolutionalMulVAE.set_kl_schedule: its parameters as plain numbers, or
+        # None): kept here because its position IS the step count `t`, and so that it rides in state_dict()
+        self.kl_schedule = None
         # True: the zero_grad ranges of flat_g are known to be zero (the last Adam launch cleared them after reading and no
         # backward kernel has accumulated since: ops._grad_buf resets it) — zero_grad() is then free
         self._clean = False
@@ -418,12 +421,19 @@ class FlatAdam:
             sd["ema"] = {"decay": self.ema_decay if self.ema_decay is not None else st["decay"], "warmup": self.ema_warmup,
                          "updates": st["updates"],
                          "avg": {n: self._to_ref(n, v).detach().cpu().contiguous() for n, v in self._ema_views()}}
+        if self.kl_schedule is not None:
+            sd["kl_schedule"] = dict(self.kl_schedule)
         return sd
 
     def load_state_dict(self, sd, legacy_layout=None):
         """legacy_layout: only for format-1 files (see below): "packed" | "torch"."""
         if sorted(sd["names"]) != sorted(self.names):
             raise ValueError("optimizer state was saved for a different set of parameters")
+        saved_kl = sd.get("kl_schedule")
+        if saved_kl is not None and self.kl_schedule is not None and dict(saved_kl) != dict(self.kl_schedule):
+            raise ValueError(f"optimizer state was trained under the KL schedule {dict(saved_kl)}, this run asks for "
+                             f"{dict(self.kl_schedule)}: resume with the same schedule (or with none: the saved one is "
+                             "restored), or start a new run")
         fmt = int(sd.get("format", 1))
         if fmt == 1:
             # raw flat vectors in the order of ITS `names`.  Two builds wrote this format and nothing in the file tells

@@ -13,6 +13,9 @@ and written as <name>_<epoch>.ema.pth next to every checkpoint; --use-ema makes 
 --val-seed and written to <log_dir>/val_split.json), the eight loss terms on it every --val-interval epochs (last iterate and,
 with --ema-decay, the average: Val/... and Val EMA/... in scalars.jsonl, per speaker in <log_dir>/val.json) and
 checkpoints/best.json naming the checkpoint with the lowest Val/Loss; --use-best makes --convert voice that one.
+--kl-schedule {constant,linear,cyclical,double} / --free-bits F (new, opt-in): KL annealing and per-dimension free bits on the
+training loss, on the device inside the replayed step (ConvolutionalMulVAE.set_kl_schedule, kl_schedule.py); KL/... in
+scalars.jsonl, <log_dir>/kl_dims.json; the schedule rides in the .opt sidecar and a resume continues it.
 --convert (reference variational_base_vae.py:243-330, minus plots): the first --convert-count sorted utterances of
 --src_spk, each with a random utterance of --trg_spk (seeded by --seed), through `convert_mel`; the converted mels are
 voiced by the GPU Griffin-Lim inverse of the mel front-end (frontend.MelInverter, --griffin-lim-iters) instead of the
@@ -103,7 +106,35 @@ def get_parse():
                    help="--convert --overlap: the style comes from the first N sorted utterances of --trg_spk (0: all)")
     p.add_argument("--style-mix", type=float, default=1.0,
                    help="--convert --overlap: 1 the target's style, 0 the source's own mean style, between: a blend")
+    p.add_argument("--kl-schedule", choices=("constant", "linear", "cyclical", "double"), default=None,
+                   help="anneal the KL weight of the training loss on the device, inside the replayed step: constant (kl_cof), "
+                        "linear (--kl-start to kl_cof over --kl-warmup-steps steps), cyclical (the same steps cut into "
+                        "--kl-cycles cycles, each ramping over its first --kl-ratio), double (--kl-start, doubled every "
+                        "epoch, capped at kl_cof: the reference's update_kl).  Validation keeps kl_cof.  Default: off")
+    p.add_argument("--kl-start", type=float, default=0.0, help="--kl-schedule: the weight the ramp starts from")
+    p.add_argument("--kl-warmup-steps", type=int, default=0, help="--kl-schedule linear / cyclical: optimiser steps of the ramp(s)")
+    p.add_argument("--kl-cycles", type=int, default=4, help="--kl-schedule cyclical: number of cycles")
+    p.add_argument("--kl-ratio", type=float, default=0.5, help="--kl-schedule cyclical: the rising part of a cycle")
+    p.add_argument("--free-bits", type=float, default=None,
+                   help="nats every latent dimension may spend unpenalised (batch-mean KL per dimension, Kingma et al. 2016); "
+                        "without --kl-schedule it implies constant")
+    p.add_argument("--free-bits-style", type=float, default=None, help="--free-bits of the style dimensions only")
+    p.add_argument("--free-bits-content", type=float, default=None, help="--free-bits of the content dimensions only")
     return p
+
+
+KL_KEYS = ("kl_schedule", "kl_start", "kl_warmup_steps", "kl_cycles", "kl_ratio", "free_bits", "free_bits_style",
+           "free_bits_content")
+
+
+def kl_schedule_args(args):
+    """(kind, keyword arguments) of ConvolutionalMulVAE.set_kl_schedule from the command line; kind None: off."""
+    style = args.free_bits_style if args.free_bits_style is not None else args.free_bits
+    content = args.free_bits_content if args.free_bits_content is not None else args.free_bits
+    fb = None if style is None and content is None else (style or 0.0, content or 0.0)
+    kind = args.kl_schedule or ("constant" if fb is not None else None)
+    return kind, dict(start=args.kl_start, steps=args.kl_warmup_steps, cycles=args.kl_cycles, ratio=args.kl_ratio,
+                      free_bits=fb)
 
 
 def get_dataset(dataset_fp, batch_size, samples_length=64, seed=None, exclude=None):
@@ -373,6 +404,9 @@ def main(argv=None):
         if all(cfg[k] == get_parse().get_default(k) for k in conv_keys):
             for k in conv_keys:     # likewise the flags of the overlapped conversion
                 del cfg[k]
+        if all(cfg[k] == get_parse().get_default(k) for k in KL_KEYS):
+            for k in KL_KEYS:       # likewise the flags of the KL schedule
+                del cfg[k]
         with open(os.path.join(args.log_dir, "config.json"), "w") as fp:
             json.dump(cfg, fp, indent=4)
     vsc = ConvolutionalMulVAE(args.dataset, args.samples_length, 80, args.latent_size, args.lr, args.alpha,
@@ -385,6 +419,12 @@ def main(argv=None):
         vsc.optimizer.set_grad_clip(args.clip_grad_norm if args.clip_grad_norm > 0 else float("inf"))
     if args.ema_decay > 0:
         vsc.optimizer.set_ema(args.ema_decay)
+    kl_kind, kl_kw = kl_schedule_args(args)
+    if kl_kind is not None:
+        try:
+            vsc.set_kl_schedule(kl_kind, **kl_kw)
+        except ValueError as e:
+            raise SystemExit(f"--kl-schedule / --free-bits: {e}")
     dp = world > 1 or os.environ.get("DVAE_FORCE_DDP", "0") == "1"
     if dp:
         setup_data_parallel(vsc, args.seed)

@@ -46,7 +46,8 @@ extern "C" {
 /* ABI revision of this header; dvae_version() of the loaded library must return exactly this (the ctypes binding
  * refuses anything else: a stale .so would misread the argument lists below).  The latent report's two entry points
  * (dvae_latent_tables, dvae_latent_lse) were added at 319 without a new revision: the change is purely additive, no
- * existing argument list, structure or constant moved. */
+ * existing argument list, structure or constant moved.  Likewise the scheduled loss (dvae_loss_fwd_sched,
+ * dvae_loss_bwd_sched, dvae_loss_sched_t, DVAE_LOSS_MAX_D): additive, and the suites of the two earlier additions pin 319. */
 #define DVAE_ABI_VERSION 319
 int dvae_version(void);
 
@@ -371,6 +372,45 @@ int dvae_loss_fwd(const dvae_loss_desc_t* desc, float* out8, void* ws, void* str
 int dvae_loss_bwd(const dvae_loss_desc_t* desc, const float* g8, float* d_recon1, float* d_recon2, float* d_recon1_hat,
                   float* d_recon2_hat, float* d_q1_mu, float* d_q1_lv, float* d_q2_mu, float* d_q2_lv, float* d_s_mu,
                   float* d_s_lv, void* stream);
+
+/* ---- the same loss with its two weights ON THE DEVICE and per-dimension free bits (Kingma et al. 2016) ----
+ * For a KL warm-up inside a captured step: a weight that is a kernel argument is baked into the graph, one that is read
+ * from `coef` follows whatever the host last copied there.  desc->mse_cof and desc->kl_cof are IGNORED.
+ * q*_mu / q*_lv are row-major [rows, D] blocks, rows = nq / D.  With lambda = free_bits:
+ *   kl_dim_k[j] = kl_scale * sum_i (1 + lv_ij - mu_ij^2 - exp(lv_ij))     (kl_scale = -0.5 / rows: the batch mean, in nats)
+ *     each term in fp32 as dvae_loss_fwd computes it, the rows added in float64 in row order by the one thread that owns
+ *     the column, one rounding at the store; no atomics: two calls give the same bits.
+ *   gate_k[j]   = kl_dim_k[j] > lambda[j] ? 1 : 0   (STRICT: a dimension exactly at lambda is free; all 1 without free_bits)
+ *   aux[k]      = sum_j max(lambda[j], kl_dim_k[j]), in float64 in dimension order, rounded once; without free_bits
+ *                 aux[0], aux[1] are out8[5], out8[6] themselves
+ *   out8[1..7]  the raw, unclamped terms: bit-identical to dvae_loss_fwd's on the same inputs, free bits or not
+ *   out8[0]     = coef[0] * (((L1_1 + L1_2) + L1_3) + L1_4) + coef[1] * (aux[0] + aux[1]), in fp32 in that order (the
+ *                 second product fused into the final sum, which is how dvae_loss_fwd's expression is compiled)
+ * Without free_bits out8[0] and all ten gradients are bit-identical to dvae_loss_fwd / dvae_loss_bwd called with
+ * mse_cof = coef[0], kl_cof = coef[1] (the same kernel bodies, instantiated on where the weights come from).
+ * bwd, element (i, j) of half k: w = (g8[0] * coef[1] * gate_k[j] + g8[5 + k]) * kl_scale, d_mu = w * (-2 mu),
+ *   d_lv = w * (1 - exp(lv)): on a free dimension nothing arrives from g8[0], what arrives from g8[5 + k] stays; on a
+ *   penalised one w is dvae_loss_bwd's, bit for bit.  The reconstruction and style gradients are dvae_loss_bwd's with
+ *   coef[0] for mse_cof; the null-output rules are dvae_loss_bwd's.  Forward is two launches, backward one, as before: the
+ *   per-dimension work is done by the single final workgroup.
+ * DVAE_EINVAL, nothing written: a null sched / coef / aux, D < 1, D > DVAE_LOSS_MAX_D, nq % D != 0, coef / free_bits / aux not
+ *   4-byte aligned, and whatever dvae_loss_fwd / dvae_loss_bwd refuse. */
+#define DVAE_LOSS_MAX_D 1024
+typedef struct {
+  const float* coef;       /* device float[8]: [0] mse_cof, [1] KL weight in effect; [2..7] reserved, read as written */
+  const float* free_bits;  /* device float[D] nats per dimension (>= 0), or null: no free bits */
+  int D;                   /* latent dimensions per row: nq % D == 0, 1 <= D <= DVAE_LOSS_MAX_D */
+} dvae_loss_sched_t;
+/* aux: device float[4 + 4*D], written by fwd, read by bwd:
+ *   [0],[1]        KL_z1, KL_z2 as they enter LOSS (with free bits: sum_j max(lambda_j, kl_dim_k[j]))
+ *   [2],[3]        dimensions of z1 / z2 that are free this step (kl_dim <= lambda), as floats
+ *   [4 .. 4+2D)    kl_dim: per-dimension batch-mean KL in nats, z1 then z2
+ *   [4+2D .. 4+4D) gate: 1.0 where the dimension is penalised (kl_dim > lambda), 0.0 where it is free */
+int dvae_loss_fwd_sched(const dvae_loss_desc_t* desc, const dvae_loss_sched_t* sched, float* out8, float* aux, void* ws,
+                        void* stream);
+int dvae_loss_bwd_sched(const dvae_loss_desc_t* desc, const dvae_loss_sched_t* sched, const float* aux, const float* g8,
+                        float* d_recon1, float* d_recon2, float* d_recon1_hat, float* d_recon2_hat, float* d_q1_mu,
+                        float* d_q1_lv, float* d_q2_mu, float* d_q2_lv, float* d_s_mu, float* d_s_lv, void* stream);
 
 /* ---- Adam over one flat parameter buffer (torch.optim.Adam at disentangled_vae.py:304) ----
  * g is multiplied by grad_scale first (1/world_size after a sum all-reduce). `step` is 1-based. */
