@@ -47,7 +47,8 @@ extern "C" {
  * refuses anything else: a stale .so would misread the argument lists below).  The latent report's two entry points
  * (dvae_latent_tables, dvae_latent_lse) were added at 319 without a new revision: the change is purely additive, no
  * existing argument list, structure or constant moved.  Likewise the scheduled loss (dvae_loss_fwd_sched,
- * dvae_loss_bwd_sched, dvae_loss_sched_t, DVAE_LOSS_MAX_D): additive, and the suites of the two earlier additions pin 319. */
+ * dvae_loss_bwd_sched, dvae_loss_sched_t, DVAE_LOSS_MAX_D): additive, and the suites of the two earlier additions pin 319.
+ * Likewise the latent map's four entry points (dvae_tsne_nn, dvae_tsne_affinities, dvae_tsne_forces, dvae_tsne_update). */
 #define DVAE_ABI_VERSION 319
 int dvae_version(void);
 
@@ -860,6 +861,48 @@ int dvae_latent_tables(const float* mu, const float* lv, const float* eps, float
                        int64_t ld, void* stream);
 int dvae_latent_lse(const float* z, const float* mu, const float* a, const float* h, int64_t ld, int D, int S,
                     const int64_t* jobs, const int64_t* jobs_host, int njobs, float* out, int64_t ldo, void* stream);
+
+/* ---- latent map: exact matrix-free t-SNE and 1-NN search (python -m dvae_amd.latent_map) ----
+ * Replaces, on the project's own latents, the 2-D projections the reference draws for its vendored speaker encoder
+ * (preprocessing/encoder/visualizations.py:164-168, UMAP) and its per-speaker latent plots (model/plot.py:23-55); the
+ * optimiser is scikit-learn's exact t-SNE (van der Maaten & Hinton 2008).  Added at 319 without a new revision: purely additive.
+ * x [N, D] fp32, leading dimension ld, 1 <= D <= DVAE_LATENT_MAX_D; columns D .. ld - 1 are never read.  No N x N table is
+ * stored: every pass recomputes d_ij = sum_d (x_id - x_jd)^2 in the difference form (dz = x_id - x_jd, acc = fma(dz, dz, acc),
+ * d ascending from +0), so d_ij and d_ji are the same bits.  A launch computes the rows [row0, row0 + nrows) against all N
+ * columns and writes those rows of its outputs only (nrows = 0: no-op).  A wave owns 64 rows, one per lane; the four waves
+ * of a workgroup take the quarters [w q, (w + 1) q), q = ceil(N / 4), of the columns in ascending order and are combined in
+ * wave order, ((w0 + w1) + w2) + w3.  Every order is a function of (N, D) alone and there are no atomics: a row's bits do not
+ * depend on the other rows of the launch, and two launches give the same bits.  All calls are asynchronous on `stream`.
+ * dvae_tsne_nn: d2min[i], arg[i] = the smallest d_ij and its j over the admissible j: j != i when group is null, otherwise
+ *   group[j] != group[i] (group [N] int32).  Ties go to the lowest j; a row without an admissible j gets +inf and -1.
+ * dvae_tsne_affinities: van der Maaten's search, per row, for the precision beta at which p_j ~ exp(-beta d'_j),
+ *   d'_j = max(d_ij - d2min[i], 0), j != i, has entropy ln perplexity: S0 = sum exp(-beta d'), S1 = sum d' exp(-beta d')
+ *   (fma), lnz = logf(S0), entropy = fma(beta, S1 / S0, lnz).  beta starts at 1, doubles (up to 2^100) or halves until
+ *   bracketed, then bisects; a row stops when |entropy - ln perplexity| <= 1e-5 (scikit-learn's tolerance) and steps[i] is
+ *   the number of evaluations it took.  After max_steps evaluations steps[i] = -1 and beta, lnz, entropy are the last
+ *   evaluation's, all finite.  With d2min from dvae_tsne_nn (group null) the nearest neighbour contributes exp(0) = 1:
+ *   lnz >= 0 and no exponent is positive.  N >= 2, 1 <= perplexity <= N - 1, max_steps >= 1.
+ * dvae_tsne_forces: one gradient evaluation at y [N, 2].  Per pair, j != i:
+ *   p = (exp(fma(-beta_i, d'_i, -lnz_i)) + exp(fma(-beta_j, d'_j, -lnz_j))) * fp32(1 / 2N),  d'_k = max(d_ij - d2min_k, 0),
+ *   q = fma(dy1, dy1, dy0 dy0), dy = y_i - y_j,  w = rcp(1 + q).
+ *   rows[i][0..7] = sum_j of p w dy0, p w dy1, w w dy0, w w dy1, w, and with want_kl = 1: p logf(p) over p > 0,
+ *   -p log1pf(q) (= p ln w), p; zeros with want_kl = 0.  Exponentials are v_exp_f32 of the argument times log2 e.
+ * dvae_tsne_update: Z = the sum of rows[.][4], and with kl non-null the three KL sums, in float64 in one fixed order (thread
+ *   t of 256 adds the rows t, t + 256, ... ascending; the 256 partial sums are then added in thread order);
+ *   *kl = sum p ln p - sum p ln w + ln Z sum p (double, 8-byte aligned, device).  Then scikit-learn's _gradient_descent rule,
+ *   element by element: g = 4 fma(ex, A, -(R fp32(1 / Z))); gains = max(upd g < 0 ? gains + 0.2 : gains 0.8, 0.01);
+ *   upd = fma(momentum, upd, -(lr (gains g))); y += upd.  y, upd, gains [N, 2].
+ * Null required pointers, N < 1, N > INT_MAX, D outside 1 .. DVAE_LATENT_MAX_D, ld < D, a row range outside [0, N], want_kl
+ *   outside {0, 1}, lr <= 0, momentum < 0, exaggeration <= 0, a misaligned kl, or (affinities) N < 2, a perplexity outside
+ *   [1, N - 1] or max_steps < 1 return DVAE_EINVAL and launch nothing. */
+int dvae_tsne_nn(const float* x, int64_t ld, int64_t N, int D, const int* group, int64_t row0, int64_t nrows, float* d2min,
+                 int* arg, void* stream);
+int dvae_tsne_affinities(const float* x, int64_t ld, int64_t N, int D, const float* d2min, float perplexity, int max_steps,
+                         int64_t row0, int64_t nrows, float* beta, float* lnz, float* entropy, int* steps, void* stream);
+int dvae_tsne_forces(const float* x, int64_t ld, int64_t N, int D, const float* beta, const float* d2min, const float* lnz,
+                     const float* y, int want_kl, int64_t row0, int64_t nrows, float* rows, void* stream);
+int dvae_tsne_update(const float* rows, int64_t N, float* y, float* upd, float* gains, float lr, float momentum,
+                     float exaggeration, double* kl, void* stream);
 
 /* ---- held-out validation (model/variational_base_vae.py: validate) ----
  * The reference's test() (variational_base_vae.py:105-123) sums loss_functionGVAE2 (disentangled_vae.py:310-327) over the
