@@ -190,6 +190,9 @@ SIGNATURES = {
     "dvae_tsne_affinities": (i32, [vp, i64, i64, i32, vp, f32, i32, i64, i64, vp, vp, vp, vp, vp]),
     "dvae_tsne_forces": (i32, [vp, i64, i64, i32, vp, vp, vp, vp, i32, i64, i64, vp, vp]),
     "dvae_tsne_update": (i32, [vp, i64, vp, vp, vp, f32, f32, f32, vp, vp]),
+    "dvae_adv_rows": (i32, [vp, i64, vp, vp, i32, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, i32,
+                            vp]),
+    "dvae_adv_params": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
     "dvae_pair_metrics": (i32, [vp] * 9 + [i32, i64, i32, i32, f32, f32, vp]),
     "dvae_group_sum_f64": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "dvae_prof_enable": (i32, [i32]),

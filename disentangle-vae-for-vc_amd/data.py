@@ -306,7 +306,10 @@ class GpuPairLoader:
         spk = np.array([self.dataset.speaker_ids.index(os.path.basename(os.path.dirname(p[0]))) for p in pairs])
         return self.gather(u1, off(u1)), self.gather(u2, off(u2)), torch.from_numpy(spk).to(self.device)
 
-    def __iter__(self):
+    def _epoch_plan(self):
+        """One epoch's batches as host arrays (utt1, utt2, off1, off2, speaker), drawn from the seeded streams in THE order an
+        epoch draws them: the permutation first, then per batch the crop offsets of the x1 half and of the x2 half.  `__iter__`
+        gathers them on the device; `skip_epochs` only draws."""
         n = len(self.dataset)
         order = self.rng.permutation(n) if self.shuffle else np.arange(n)     # identical on every rank
         order = order[:self._n_local() * self.world_size][self.rank::self.world_size]
@@ -318,5 +321,20 @@ class GpuPairLoader:
             o1 = np.array([self._offset(int(self.lengths[u])) for u in u1], dtype=np.int32)
             o2 = np.array([self._offset(int(self.lengths[u])) for u in u2], dtype=np.int32)
             spk = np.array([self.dataset.speaker_ids.index(os.path.basename(os.path.dirname(p[0]))) for p in pairs])
+            yield u1, u2, o1, o2, spk
+
+    def skip_epochs(self, epochs: int):
+        """Advance the seeded streams (the epoch permutation, the crop offsets, the dataset's re-pairing) past `epochs` whole
+        epochs without touching the device: what a resumed run calls so that epoch e feeds the batches the uninterrupted run
+        fed in epoch e.  Without a seed the streams are numpy's global ones and there is nothing to replay."""
+        if self.rng is np.random:
+            return
+        for _ in range(int(epochs)):
+            for _ in self._epoch_plan():
+                pass
+            self.dataset.shuffle_data()      # what train() does at the end of an epoch
+
+    def __iter__(self):
+        for u1, u2, o1, o2, spk in self._epoch_plan():
             self.last_meta = (u1, u2, o1, o2)
             yield self.gather(u1, o1), self.gather(u2, o2), torch.from_numpy(spk).to(self.device)

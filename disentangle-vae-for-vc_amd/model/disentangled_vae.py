@@ -415,7 +415,7 @@ class DisentangledVAE(nn.Module):
 
     def forward_full(self, x1, x2, train=True, eps_style=None):
         """The forward pass with its outputs UNSPLIT: (rec, rec_hat, q_mu, q_lv, s_mu, s_lv) with rec / rec_hat [2*Bh, 80, T]
-        and q_mu / q_lv [2*Bh, Cn] holding the x1 half first.  `forward` returns the reference's ten tensors as views of
+        and q_mu / q_lv [2*Bh, S + Cn] (the style block first, then the content block) holding the x1 half first. `forward` returns the reference's ten tensors as views of
         these; the training step hands the unsplit tensors to the fused loss (ops.LossGVAE2FullFn), so that autograd
         has no slice to undo (each `t[:Bh]` costs a zero-fill and a copy in backward).
         eps_style (train=False only): the style noise [Bh, S] of the inference pass, which the reference samples in eval
@@ -555,6 +555,46 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         self.kl_sched = sched
         opt.kl_schedule = sched.params()        # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
         self._kl_sent, self._kl_k, self.kl_weight = None, None, None
+
+    def set_speaker_adversary(self, weight=None, *, n_speakers=None, hidden=256, lr=1e-3, warmup_steps=0, seed=0):
+        """A speaker classifier on the content means of every TRAINING step, trained inside the replayed graph, whose
+        gradient reaches the encoder reversed and scaled by lambda (adversary.py).  weight: None (off:
+        the step launches what it launched without this, under the same graph signature) or >= 0; 0 is a live leakage
+        monitor — the classifier learns, the model's step keeps its bits.  lambda = weight min(1, k / warmup_steps) at the
+        model optimiser's step count k (`weight` when warmup_steps is 0): a device scalar refreshed by one small copy before
+        the step, never a new capture.  The classifier has an optimiser of its own (Adam, `lr`); the weight average
+        (FlatAdam.set_ema) does not cover it, and validation, `Val/Loss` and checkpoints/best.json do not see it: epochs stay
+        compared under one fixed objective.  `step` / `step_async` then need `speaker_ids`.  `train()` reports Adv/CE,
+        Adv/Accuracy (of the classifier on the training batches, while it learns) and Adv/Weight in `adv_stats`.
+        Not data parallel: with a reducer attached this raises, and attach_reducer raises while it is on."""
+        if weight is None:
+            self.adversary, self.adv_config = None, None
+            return
+        from ..adversary import SpeakerAdversary
+        weight, warmup_steps = float(weight), int(warmup_steps)
+        if not (weight >= 0.0 and math.isfinite(weight)) or warmup_steps < 0:
+            raise ValueError(f"set_speaker_adversary: weight {weight} >= 0 and warmup_steps {warmup_steps} >= 0")
+        if n_speakers is None:
+            raise ValueError("set_speaker_adversary: n_speakers (the number of speakers of the corpus) is required")
+        if self.reducer is not None:
+            raise ValueError("set_speaker_adversary: the adversary is not trained data parallel (a reducer is attached)")
+        dev = self.optimizer.flat_p.device
+        if dev.type != "cuda":
+            raise RuntimeError("set_speaker_adversary: the adversary runs only on the HIP device (no CPU fallback)")
+        Cn = self.model.latent_dim - self.model.speaker_size
+        cfg = dict(weight=weight, n_speakers=int(n_speakers), hidden=int(hidden), lr=float(lr), warmup_steps=warmup_steps,
+                   seed=int(seed))
+        old = getattr(self, "adv_config", None)
+        same_net = getattr(self, "adversary", None) is not None and \
+            all(old[k] == cfg[k] for k in ("n_speakers", "hidden", "lr", "seed"))
+        if not same_net:        # a new classifier; only the weight or its warm-up changed: the one that is learning stays
+            self.adversary = SpeakerAdversary(Cn, n_speakers, hidden=hidden, seed=seed, device=dev, lr=lr)
+        if getattr(self, "_adv_coef", None) is None:        # allocated once: a captured graph holds its address
+            self._adv_coef = torch.zeros(1, device=dev, dtype=torch.float32)
+            self._adv_pin, self._adv_pin_ev, self._adv_pin_i = None, None, 0
+        self.adv_config = cfg
+        self._adv_sent, self._adv_k, self.adv_weight = None, None, None
+        self.adv_out = self.adv_pred = self.adv_stats = None
 
     def kl_weight_at(self, k, epoch=1):
         """The KL weight of the step that runs after `k` optimiser steps, in epoch `epoch` (kl_schedule.KLSchedule)."""

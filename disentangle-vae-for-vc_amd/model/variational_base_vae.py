@@ -63,6 +63,9 @@ class VariationalBaseModelVAE:
 
     # ---- data parallel (new functionality: the reference is single-device)
     def attach_reducer(self, reducer):
+        if reducer is not None and getattr(self, "adversary", None) is not None:
+            raise ValueError("attach_reducer: the speaker adversary (set_speaker_adversary) is not trained data parallel: its "
+                             "gradients are not reduced; switch it off first")
         sharded = reducer is not None and getattr(reducer, "mode", "all_reduce") == "rs_ag"
         if sharded and self.optimizer is not None:
             from ..ddp import refuse_sharded_clip, refuse_sharded_ema
@@ -115,7 +118,58 @@ class VariationalBaseModelVAE:
         return (tuple(data1.shape), tuple(opt.betas), float(opt.eps)) + cofs + (
                 int(self.batch_size), bool(self.model.training),
                 self.reducer is not None, getattr(self.reducer, "world_size", 1), ops.current_mode(),
-                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature() + kl
+                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature() + kl + self._adv_signature()
+
+    def _adv_signature(self):
+        """The speaker adversary on/off and its shape change the launches of a step; its weight does not (a device scalar,
+        _sync_adv_coef).  Nothing is added while it is off."""
+        adv = getattr(self, "adversary", None)
+        return (("adv", adv.hidden, adv.n_speakers),) if adv is not None else ()
+
+    def adv_weight_at(self, k):
+        """The reversal weight of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
+        cfg = self.adv_config
+        w, n = float(cfg["weight"]), int(cfg["warmup_steps"])
+        return w if n <= 0 else w * min(1.0, k / n)
+
+    def _sync_adv_coef(self):
+        """Host -> device copy of the reversal weight of the step about to run when it changed since the last copy; beside
+        _sync_kl_coef, never inside a capture.  The step's number is the model optimiser's step count, kept by the host as
+        `_adv_k` exactly as `_kl_k` is."""
+        if getattr(self, "adversary", None) is None:
+            return
+        if self._adv_k is None:
+            self._adv_k = self.optimizer.t
+        w = float(self.adv_weight_at(self._adv_k))
+        if w != self._adv_sent:
+            if self._adv_pin is None:
+                self._adv_pin = torch.empty(16, 1, dtype=torch.float32, pin_memory=True)
+                self._adv_pin_ev = [None] * 16
+            i = self._adv_pin_i = (self._adv_pin_i + 1) % 16
+            if self._adv_pin_ev[i] is not None:
+                self._adv_pin_ev[i].synchronize()
+            self._adv_pin[i, 0] = w
+            self._adv_coef[0:1].copy_(self._adv_pin[i], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._adv_pin_ev[i] = ev
+            self._adv_sent = w
+        self.adv_weight = w
+        self._adv_k += 1
+
+    def _adv_labels(self, speaker_ids, out=None):
+        """speaker_ids [Bh] (host or device, any integer type) -> the [2 Bh] int32 device labels of the rows of q_mu (the x1
+        half, then the x2 half: the same speakers); `out`: the static buffer of a captured step."""
+        if speaker_ids is None:
+            raise ValueError("the speaker adversary is on (set_speaker_adversary): step / step_async need speaker_ids")
+        ids = torch.as_tensor(speaker_ids).view(-1).to(device=self.device, dtype=torch.int32)
+        if out is None:
+            return torch.cat([ids, ids])
+        if out.numel() != 2 * ids.numel():
+            raise ValueError(f"speaker_ids: {ids.numel()} labels for a batch of {out.numel() // 2} pairs")
+        out[:ids.numel()].copy_(ids)
+        out[ids.numel():].copy_(ids)
+        return out
 
     def _kl_signature(self):
         """A KL schedule on/off, and free bits on/off, change the loss launches of a step; the weight does not (a device
@@ -169,20 +223,45 @@ class VariationalBaseModelVAE:
         averages already, and are the same inside and outside."""
         return self.optimizer.ema_weights()
 
-    def _eager_train_step(self, data1, data2, kl_sent=False):
+    def _eager_train_step(self, data1, data2, kl_sent=False, labels2=None):
         # (until round 5 the step ran inside an ops.ZeroArena: one clear launch for the outputs that split-k contractions
         # accumulated into atomically; split contractions store slabs now and nothing needs clearing)
         if not kl_sent:                 # _step_graph sends the weights of a KL schedule itself, before capture / replay
             self._sync_kl_coef()
-        return self._train_step_body(data1, data2)
+            self._sync_adv_guard()
+            self._sync_adv_coef()       # likewise the adversary's reversal weight
+        return self._train_step_body(data1, data2, labels2)
 
-    def _train_step_body(self, data1, data2):
+    def _sync_adv_guard(self):
+        """The guard of the model's optimiser covers the adversary's: a step the one skips on a non-finite gradient must not
+        feed NaNs into the other's moments.  The first set_grad_clip allocates: like every other host-side refresh this runs
+        before the step, never inside a capture (the model's guard is part of the graph signature, so switching it captures
+        again, after this)."""
+        adv = getattr(self, "adversary", None)
+        if adv is None:
+            return
+        guard = getattr(self.optimizer, "max_norm", None) is not None
+        if guard != (adv.optimizer.max_norm is not None):
+            adv.optimizer.set_grad_clip(float("inf") if guard else None, skip_nonfinite=True)
+
+    def _train_step_body(self, data1, data2, labels2=None):
         self.optimizer.zero_grad()
+        adv = getattr(self, "adversary", None)
+        outs = None
+        if adv is not None:
+            if labels2 is None:
+                raise ValueError("the speaker adversary is on (set_speaker_adversary): the step needs speaker_ids")
+            if not (hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full")):
+                raise RuntimeError("the speaker adversary needs the unsplit forward (forward_full / losses_vector_full)")
+            if self.reducer is not None:
+                raise ValueError("the speaker adversary is not trained data parallel")
+            adv.optimizer.zero_grad()       # store-first parameters only: no launch, the written-once counts start over
         if hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full"):
             # the eight scalars as one vector (fused loss kernels) on the UNSPLIT outputs; backward is seeded with the
             # constant (1, 0, ..., 0): `vec[0].backward()` and the reference's ten output slices cost ~25 zero-fill /
             # copy launches of autograd glue per step
-            vec = self.losses_vector_full(data1, data2, *self.model.forward_full(data1, data2))
+            outs = self.model.forward_full(data1, data2)
+            vec = self.losses_vector_full(data1, data2, *outs)
             losses = None
         else:
             vec = None
@@ -193,7 +272,17 @@ class VariationalBaseModelVAE:
             if getattr(self, "_loss_seed", None) is None or self._loss_seed.device != vec.device:
                 self._loss_seed = torch.zeros(8, device=vec.device)
                 self._loss_seed[0] = 1.0
-            torch.autograd.backward(vec, self._loss_seed)
+            if adv is not None:
+                # q_mu [2 Bh, S + Cn]: the content means are its columns S .. S + Cn - 1; both launches run here, the
+                # classifier's gradients land in its optimiser's buffer, and ONE backward adds the reversed gradient of
+                # q_mu to the loss's own
+                from .. import ops
+                stats = {}
+                ce = adv.loss(outs[2], labels2, self._adv_coef, self.model.speaker_size, stats)
+                self.adv_out, self.adv_pred = stats["out"], stats["row_pred"]
+                torch.autograd.backward([vec, ce], [self._loss_seed, ops.unit_seed(vec.device)])
+            else:
+                torch.autograd.backward(vec, self._loss_seed)
         else:
             losses[0].backward()
         if self.reducer is not None:
@@ -201,16 +290,19 @@ class VariationalBaseModelVAE:
             self.reducer.step(self.optimizer)       # full Adam after an all-reduce, or the sharded step (mode "rs_ag")
         else:
             self.optimizer.step(grad_scale=1.0)
+        if adv is not None:
+            adv.optimizer.step(grad_scale=1.0)
         return vec.detach() if vec is not None else torch.stack([l.detach() for l in losses])
 
-    def _step_graph(self, data1, data2):
+    def _step_graph(self, data1, data2, speaker_ids=None):
         m = self.model
         dev = data1.device
         Bh = data1.shape[0]
         S, Cn = m.speaker_size, m.latent_dim - m.speaker_size
         self._graph_calls += 1
+        adv = getattr(self, "adversary", None)
         if self._graph_calls == 1:
-            return self._eager_train_step(data1, data2)
+            return self._eager_train_step(data1, data2, labels2=self._adv_labels(speaker_ids) if adv is not None else None)
         sig = self._graph_signature(data1)
         if self._graph is not None and sig != self._graph_sig:
             self._graph = None          # a baked-in scalar or the batch shape changed: capture again
@@ -221,8 +313,11 @@ class VariationalBaseModelVAE:
             eps_c = torch.empty((2 * Bh, Cn), device=dev)
             self._g_eps_c = eps_c
             self._g_eps = (eps_c[:Bh], eps_c[Bh:], torch.empty((Bh, S), device=dev))
+            self._g_labels2 = torch.empty(2 * Bh, device=dev, dtype=torch.int32) if adv is not None else None
         self._g_x1.copy_(data1)
         self._g_x2.copy_(data2)
+        if adv is not None:
+            self._adv_labels(speaker_ids, self._g_labels2)
         user_eps = m.eps_override
         if user_eps is None:               # the eager step's two draws (content [2*Bh, Cn], style [Bh, S]), same order
             self._g_eps_c.normal_()
@@ -234,6 +329,12 @@ class VariationalBaseModelVAE:
         # learning rate / gradient scale: device scalars, refreshed OUTSIDE the captured region
         self.optimizer.sync_scalars(1.0 / self.reducer.world_size if self.reducer is not None else 1.0)
         self._sync_kl_coef()            # likewise the loss weights of a KL schedule (nothing while it is off)
+        if adv is not None:
+            from .. import ops
+            ops.unit_seed(dev)          # allocated outside the capture
+            self._sync_adv_guard()      # ... as are the buffers of the adversary's non-finite guard
+            adv.optimizer.sync_scalars(1.0)
+            self._sync_adv_coef()       # ... and the adversary's reversal weight
         if self._graph is not None and not getattr(self.optimizer, "_clean", True):
             # something accumulated into the gradient buffer since the last Adam launch (a manual backward between two
             # replays): a graph captured on a clean buffer holds no zero_grad launch of its own
@@ -261,7 +362,7 @@ class VariationalBaseModelVAE:
                     _time.sleep(0.5)
                 try:
                     with torch.cuda.graph(g, **mode):
-                        self._g_losses = self._eager_train_step(self._g_x1, self._g_x2, kl_sent=True)
+                        self._g_losses = self._eager_train_step(self._g_x1, self._g_x2, kl_sent=True, labels2=self._g_labels2)
                 except Exception as e:      # nothing of the step has run: fall back to the eager step, for good
                     if self.reducer is None:
                         raise
@@ -271,7 +372,7 @@ class VariationalBaseModelVAE:
                     self._use_graph = False
                     self._graph = None
                     torch.cuda.synchronize()
-                    return self._eager_train_step(self._g_x1, self._g_x2, kl_sent=True)
+                    return self._eager_train_step(self._g_x1, self._g_x2, kl_sent=True, labels2=self._g_labels2)
                 self._graph = g
             self._graph.replay()
             if getattr(self.optimizer, "fold_zero_grad", False):
@@ -285,15 +386,19 @@ class VariationalBaseModelVAE:
         host can enqueue the next step (noise draw, input copies, graph launch) while this one runs.  `step(...,
         train=True)` is this plus one device->host copy."""
         if self._use_graph and (self.reducer is None or self._graph_ddp):
-            return self._step_graph(data1, data2)
-        return self._eager_train_step(data1, data2)
+            return self._step_graph(data1, data2, speaker_ids)
+        adv = getattr(self, "adversary", None)
+        return self._eager_train_step(data1, data2, labels2=self._adv_labels(speaker_ids) if adv is not None else None)
 
     # ---- variational_base_vae.py:58-70
     def step(self, data1, data2, speaker_ids, train=False):
-        if train and getattr(self, "kl_sched", None) is not None:
+        if train and (getattr(self, "kl_sched", None) is not None or getattr(self, "adversary", None) is not None):
             # the same one copy carries the optimiser's step count: the schedule's position is exactly t (a skipped step)
             vec = torch.cat([self.step_async(data1, data2, speaker_ids), self.optimizer.dev_state[0:1]]).tolist()
-            self._kl_k = int(vec[8])
+            if getattr(self, "kl_sched", None) is not None:
+                self._kl_k = int(vec[8])
+            if getattr(self, "adversary", None) is not None:
+                self._adv_k = int(vec[8])
             self._check_and_recover()
             return tuple(vec[:8])
         if train:
@@ -349,12 +454,19 @@ class VariationalBaseModelVAE:
             kD = (self.kl_aux.numel() - 4) // 4
             ksum = torch.zeros(2 + 2 * kD, dtype=torch.float64, device=self.device)
             ksteps = 0
+        # the speaker adversary on (set_speaker_adversary): its four statistics of every step join a running float64 tensor
+        adv = getattr(self, "adversary", None)
+        self.adv_stats = None
+        if adv is not None:
+            asum = torch.zeros(4, dtype=torch.float64, device=self.device)
         for data1, data2, speaker_ids in train_loader:
             data1 = data1.to(self.device, non_blocking=True).float()
             data2 = data2.to(self.device, non_blocking=True).float()
             speaker_ids = speaker_ids.view(-1)
             last = self.step_async(data1, data2, speaker_ids)
             tot.add_(last)
+            if adv is not None:
+                asum.add_(self.adv_out)
             if sched is not None:
                 ksum.add_(self.kl_aux[2:4 + 2 * kD])
                 ksteps += 1
@@ -363,6 +475,13 @@ class VariationalBaseModelVAE:
                 norm = torch.where(ok, opt.clip_state[1:2], zero)
                 gsum.add_(torch.cat([norm, ok.float()]))
                 torch.maximum(gmax, norm, out=gmax)
+        if adv is not None:
+            # one more small copy per epoch: the sums, and the optimiser's step count to set the weight's position right
+            a = torch.cat([asum, opt.dev_state[0:1].double()]).tolist()
+            self._adv_k = int(a[4])
+            self.adv_stats = {"Adv/CE": a[0] / a[1] if a[1] else float("nan"),
+                              "Adv/Accuracy": a[2] / a[1] if a[1] else float("nan"),
+                              "Adv/Weight": self.adv_weight if self.adv_weight is not None else self.adv_weight_at(self._adv_k)}
         ktail = []
         if sched is not None:
             tot = torch.cat([tot, ksum, opt.dev_state[0:1].double()])     # behind the eight sums, in front of the rest
@@ -492,9 +611,13 @@ class VariationalBaseModelVAE:
         return self.validate(test_loader, logging_func)["Val/Loss"]
 
     # ---- variational_base_vae.py:127-149
-    def load_last_model(self, checkpoints_path, logging_func=print, use_ema=False):
+    def load_last_model(self, checkpoints_path, logging_func=print, use_ema=False, restore_adversary=False):
         """use_ema: take the weights from `<base>.ema.pth` (the averaged weights run_training writes next to `<base>.pth`
-        while FlatAdam.set_ema is on) in place of `<base>.pth`.  A `<epoch>.ema` stem is never a checkpoint candidate."""
+        while FlatAdam.set_ema is on) in place of `<base>.pth`.  A `<epoch>.ema` stem is never a checkpoint candidate.
+        The speaker adversary's sidecar `<base>.adv.pth` matters only to a trainer that trains: with an adversary switched on
+        it is loaded (and a different or a missing one refused); with none, it is restored from the sidecar only under
+        `restore_adversary` (run_training), and otherwise left alone — conversion, probing and the reports load a checkpoint
+        of an adversary run exactly as they load any other."""
         name = self.model.__class__.__name__
         ids = []
         for f in glob(f"{checkpoints_path}/*.pth"):
@@ -511,7 +634,28 @@ class VariationalBaseModelVAE:
             if not os.path.exists(weights):
                 raise FileNotFoundError(f"{weights} is missing: the last checkpoint ({last}) was written without a weight "
                                         "average (train with --ema-decay / FlatAdam.set_ema)")
+        # the speaker adversary of the run (`<base>.adv.pth`): checked before anything is loaded
+        adv_path, adv_sd = last[:-4] + ".adv.pth", None
+        if getattr(self, "adversary", None) is None and not restore_adversary:
+            pass
+        elif os.path.exists(adv_path):
+            adv_sd = torch.load(adv_path, map_location="cpu")
+            want = getattr(self, "adv_config", None) if getattr(self, "adversary", None) is not None else None
+            if want is not None and dict(want) != dict(adv_sd["config"]):
+                raise ValueError(f"{adv_path} was trained with the speaker adversary {dict(adv_sd['config'])}, this run asks "
+                                 f"for {dict(want)}: resume with the same flags (or with none: the saved ones are restored), or "
+                                 "start a new run")
+        elif getattr(self, "adversary", None) is not None:
+            raise ValueError(f"{adv_path} is missing: the last checkpoint ({last}) was written without a speaker adversary, "
+                             "and one cannot join a run half way (its classifier would start untrained against a trained "
+                             "encoder); start a new run")
         self.model.load_state_dict(torch.load(weights, map_location=self.device))
+        if adv_sd is not None and not use_ema and hasattr(self, "set_speaker_adversary"):
+            if getattr(self, "adversary", None) is None:
+                cfg = dict(adv_sd["config"])
+                self.set_speaker_adversary(cfg.pop("weight"), **cfg)
+            self.adversary.load_state_dict(adv_sd["adversary"])
+            self._adv_k = None
         opt = last[:-4] + ".opt"
         if os.path.exists(opt):
             sd = torch.load(opt, map_location="cpu")
@@ -552,6 +696,10 @@ class VariationalBaseModelVAE:
         was_training = self.model.training
         self.model.eval()
         os.makedirs(estimation_dir, exist_ok=True)
+        # the eval-mode forward draws its style noise from the default generator: put the generator back where the checkpoint
+        # recorded it, so that the epochs behind this checkpoint draw what a run resumed from it draws
+        cuda = torch.device(self.device).type == "cuda"
+        rng = torch.cuda.get_rng_state(self.device) if cuda else None
         try:
             # a loader with sample_batch (data.GpuPairLoader) hands out a batch WITHOUT advancing its epoch streams: under
             # data parallelism only rank 0 comes here and must not fall out of step with the other ranks' permutations
@@ -582,6 +730,8 @@ class VariationalBaseModelVAE:
             return logging_epoch, recons_x1, recons_x2
         finally:
             self.model.train(was_training)
+            if rng is not None:
+                torch.cuda.set_rng_state(rng, self.device)
 
     # ---- tensor part of voice_conversion_mel (variational_base_vae.py:269-301); file I/O, plots and the WaveNet
     # vocoder of the reference stay outside
@@ -667,7 +817,10 @@ class VariationalBaseModelVAE:
         checkpoint epoch rank 0 runs `validate` — on the average too while FlatAdam.set_ema is on — its numbers join the
         epoch's record, `val.json` beside `logs_path` (the command line's <log_dir>) holds the per-speaker table of the last pass, and the checkpoint with the
         lowest `Val/Loss` so far (last iterate or average) is named by `<checkpoints_path>/best.json`."""
-        start_epoch = self.load_last_model(checkpoints_path, logging_func) if reload_model else 1
+        start_epoch = self.load_last_model(checkpoints_path, logging_func, restore_adversary=True) if reload_model else 1
+        if start_epoch > 1 and hasattr(train_loader, "skip_epochs"):
+            # a resumed run feeds epoch e what the uninterrupted run fed it (data.GpuPairLoader: seeded streams, replayed)
+            train_loader.skip_epochs(start_epoch - 1)
         run_name = "DisentangledVAE_VCTK"
         log_f = None
         if logs_path and self._is_rank0():
@@ -684,6 +837,8 @@ class VariationalBaseModelVAE:
                 rec.update(self.grad_stats)
             if getattr(self, "ema_stats", None):        # weight average on (FlatAdam.set_ema)
                 rec.update(self.ema_stats)
+            if getattr(self, "adv_stats", None):        # speaker adversary on (set_speaker_adversary)
+                rec.update(self.adv_stats)
             if getattr(self, "kl_stats", None):         # KL schedule on (set_kl_schedule)
                 rec.update(self.kl_stats)
                 if logs_path and self._is_rank0():
@@ -723,6 +878,10 @@ class VariationalBaseModelVAE:
                     gen = torch.cuda.default_generators[torch.device(self.device).index or 0]
                     osd["cuda_rng_seed"], osd["cuda_rng_offset"] = int(gen.initial_seed()), int(gen.get_offset())
                     torch.save(osd, base + ".opt")
+                    if getattr(self, "adversary", None) is not None:
+                        # beside it: the speaker adversary (the .pth keeps the reference's keys)
+                        torch.save({"config": dict(self.adv_config), "adversary": self.adversary.state_dict()},
+                                   base + ".adv.pth")
                     if getattr(self.optimizer, "ema_decay", None) is not None:
                         # the very state_dict above with every parameter replaced by its average; buffers (BatchNorm
                         # running statistics) are the same tensors in both files

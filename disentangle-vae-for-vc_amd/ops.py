@@ -1655,6 +1655,104 @@ class SoftmaxCeFn(torch.autograd.Function):
         return dx, None, None, None
 
 
+# ----------------------------------------------------------------------------- speaker adversary (adversary.py)
+ADV_MAX_D, ADV_MAX_H = 64, 1024     # DVAE_ADV_MAX_D, DVAE_ADV_MAX_H
+_unit_seeds: dict = {}
+
+
+def unit_seed(dev) -> torch.Tensor:
+    """THE gradient SpeakerAdversaryFn.backward accepts: a device scalar 1.0, one per device, never written again."""
+    key = _dev_index(dev)
+    t = _unit_seeds.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ops.unit_seed would allocate during a graph capture: run one eager step first")
+        t = _unit_seeds[key] = torch.ones((), device=dev, dtype=torch.float32)
+    return t
+
+
+def speaker_adversary(x, labels, w1, b1, w2, b2, coef, col0=0, dim=None, grads=None):
+    """dvae_adv_rows + dvae_adv_params on the columns [col0, col0 + dim) of x [R, L] (read in place) and int32 labels [R]
+    (negative or >= S: the row is ignored).  w1 [H, dim_p], b1 [H], w2 [S, H], b2 [>= S]; coef a device float holding the
+    reversal weight.  grads: None (evaluation: the statistics only) or the four tensors (dw1, db1, dw2, db2), which are
+    STORED into.  -> (out [4] = {loss sum, counted rows, correct rows, loss sum / R}, row_pred [R] int32, dx [R, L]: the
+    reversed gradient in x's columns, +0.0 in the others)."""
+    _ok(x, w1, b1, w2, b2, coef)
+    if x.dim() != 2 or w1.dim() != 2 or w2.dim() != 2:
+        raise ValueError("speaker_adversary: x [R, L], w1 [H, dim_p], w2 [S, H]")
+    R, L = x.shape
+    col0 = int(col0)
+    D = L - col0 if dim is None else int(dim)
+    H, ldw1 = w1.shape
+    S = w2.shape[0]
+    if not (labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and labels.numel() == R):
+        raise ValueError("speaker_adversary: one contiguous int32 GPU label per row of x")
+    if not (col0 >= 0 and D >= 1 and col0 + D <= L and w2.shape[1] == H and b1.numel() == H and b2.numel() >= S
+            and coef.numel() >= 1):
+        raise ValueError("speaker_adversary: shapes do not fit (x columns, w1 [H, dim_p], b1 [H], w2 [S, H], b2 [S])")
+    dev = x.device
+    row_loss = torch.empty(R, device=dev, dtype=torch.float32)
+    row_pred = torch.empty(R, device=dev, dtype=torch.int32)
+    h = torch.empty((R, H), device=dev, dtype=torch.float32)
+    g1 = torch.empty_like(h)
+    g2 = torch.empty((R, S), device=dev, dtype=torch.float32)
+    dx = torch.empty((R, L), device=dev, dtype=torch.float32)
+    out = torch.empty(4, device=dev, dtype=torch.float32)
+    inv_rows = 1.0 / R
+    xp = x.data_ptr() + 4 * col0
+    L_ = lib()
+    check(L_.dvae_adv_rows(xp, L, ptr(labels), ptr(w1), ldw1, ptr(b1), ptr(w2), ptr(b2), ptr(coef), inv_rows, R, D, H, S,
+                           ptr(row_loss), ptr(row_pred), ptr(h), ptr(g2), ptr(g1), ptr(dx), L, col0, stream()),
+          "dvae_adv_rows")
+    dw1, db1, dw2, db2 = grads if grads is not None else (None,) * 4
+    check(L_.dvae_adv_params(xp, L, ptr(labels), ptr(h), ptr(g2), ptr(g1), ptr(row_loss), ptr(row_pred), inv_rows, R, D, H, S,
+                             ptr(dw1), ldw1, ptr(db1), ptr(dw2), ptr(db2), ptr(out), stream()), "dvae_adv_params")
+    return out, row_pred, dx
+
+
+class SpeakerAdversaryFn(torch.autograd.Function):
+    """Cross-entropy of the speaker classifier Linear -> ReLU -> Linear on the columns [col0, col0 + dim) of q_mu, summed over
+    the counted rows and divided by ALL rows (a device scalar), as two launches that run in `forward` and leave every
+    gradient behind, as SoftmaxCeFn does: the classifier's own gradients are stored straight into its parameters' `.grad`
+    (the flat gradient buffer of adversary.SpeakerAdversary's optimiser), and the gradient of q_mu is REVERSED and scaled by
+    the device scalar `coef` (Ganin & Lempitsky 2015).  `backward` hands that gradient to q_mu and nothing else; the incoming
+    gradient is taken as 1, so it must BE `ops.unit_seed(device)`: any other use (a weighted sum with the loss, .backward() on a
+    function of the result) is refused.  `stats` (a dict, optional) receives `out` and `row_pred`."""
+
+    @staticmethod
+    def forward(ctx, q_mu, labels, w1, b1, w2, b2, coef, col0=0, dim=None, stats=None):
+        params = (w1, b1, w2, b2)
+        train = any(p.requires_grad for p in params)
+        grads = None
+        if train:
+            if not all(p.requires_grad for p in params):
+                raise ValueError("SpeakerAdversaryFn: all four parameters take a gradient, or none")
+            grads = tuple(_grad_buf(p) for p in params)
+        out, row_pred, dx = speaker_adversary(q_mu, labels, w1, b1, w2, b2, coef, col0, dim, grads)
+        if train:
+            for p in params:      # FlatAdam.step checks a store-first gradient: written exactly once
+                if getattr(p, "_dvae_grad_store_first", False):
+                    p._dvae_sf_writes = getattr(p, "_dvae_sf_writes", 0) + 1
+        if stats is not None:
+            stats["out"], stats["row_pred"] = out, row_pred
+        ctx.save_for_backward(dx)
+        ctx.seed_ptr = unit_seed(q_mu.device).data_ptr()
+        return out[3]
+
+    @staticmethod
+    def backward(ctx, g):
+        # (the seed is recognised by its address: this relies on autograd handing a root gradient to the root's function as
+        # the tensor it was given, neither copied nor accumulated — true of torch's engine, which clones a root gradient only
+        # when it has to add to it, and pinned by tests/test_hip_adversary_train.py; a torch that copied it would make every
+        # step raise here, loudly, not train wrongly)
+        if g.data_ptr() != ctx.seed_ptr:
+            raise RuntimeError("SpeakerAdversaryFn.backward: the incoming gradient must be ops.unit_seed(device) "
+                               "(torch.autograd.backward([..., ce], [..., ops.unit_seed(device)])): the gradients were "
+                               "computed in forward for a seed of 1 and cannot be rescaled")
+        dx, = ctx.saved_tensors
+        return dx, None, None, None, None, None, None, None, None, None
+
+
 def prof_enable(family: int):
     check(lib().dvae_prof_enable(family), "dvae_prof_enable")
 

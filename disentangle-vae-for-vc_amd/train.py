@@ -16,6 +16,10 @@ checkpoints/best.json naming the checkpoint with the lowest Val/Loss; --use-best
 --kl-schedule {constant,linear,cyclical,double} / --free-bits F (new, opt-in): KL annealing and per-dimension free bits on the
 training loss, on the device inside the replayed step (ConvolutionalMulVAE.set_kl_schedule, kl_schedule.py); KL/... in
 scalars.jsonl, <log_dir>/kl_dims.json; the schedule rides in the .opt sidecar and a resume continues it.
+--adv-weight F (new, opt-in): a speaker classifier on the content means, trained inside the replayed step, whose gradient
+reaches the encoder reversed and scaled by F (ConvolutionalMulVAE.set_speaker_adversary, adversary.py; 0: it only monitors);
+--adv-hidden, --adv-lr, --adv-warmup-steps; Adv/... in scalars.jsonl; it is checkpointed as <name>_<epoch>.adv.pth beside the
+.pth, and a resume continues it (without the flags: with the saved configuration).
 --convert (reference variational_base_vae.py:243-330, minus plots): the first --convert-count sorted utterances of
 --src_spk, each with a random utterance of --trg_spk (seeded by --seed), through `convert_mel`; the converted mels are
 voiced by the GPU Griffin-Lim inverse of the mel front-end (frontend.MelInverter, --griffin-lim-iters) instead of the
@@ -120,9 +124,18 @@ def get_parse():
                         "without --kl-schedule it implies constant")
     p.add_argument("--free-bits-style", type=float, default=None, help="--free-bits of the style dimensions only")
     p.add_argument("--free-bits-content", type=float, default=None, help="--free-bits of the content dimensions only")
+    p.add_argument("--adv-weight", type=float, default=None,
+                   help="train a speaker classifier on the content means inside the step and send its gradient to the encoder "
+                        "reversed, scaled by this weight (0: the classifier learns, the model is untouched: a leakage monitor). "
+                        "Default: off")
+    p.add_argument("--adv-hidden", type=int, default=256, help="--adv-weight: hidden width of the classifier (a multiple of 64)")
+    p.add_argument("--adv-lr", type=float, default=1e-3, help="--adv-weight: learning rate of the classifier's own Adam")
+    p.add_argument("--adv-warmup-steps", type=int, default=0,
+                   help="--adv-weight: the weight rises linearly from 0 over this many optimiser steps")
     return p
 
 
+ADV_KEYS = ("adv_weight", "adv_hidden", "adv_lr", "adv_warmup_steps")
 KL_KEYS = ("kl_schedule", "kl_start", "kl_warmup_steps", "kl_cycles", "kl_ratio", "free_bits", "free_bits_style",
            "free_bits_content")
 
@@ -407,6 +420,9 @@ def main(argv=None):
         if all(cfg[k] == get_parse().get_default(k) for k in KL_KEYS):
             for k in KL_KEYS:       # likewise the flags of the KL schedule
                 del cfg[k]
+        if all(cfg[k] == get_parse().get_default(k) for k in ADV_KEYS):
+            for k in ADV_KEYS:      # likewise the flags of the speaker adversary
+                del cfg[k]
         with open(os.path.join(args.log_dir, "config.json"), "w") as fp:
             json.dump(cfg, fp, indent=4)
     vsc = ConvolutionalMulVAE(args.dataset, args.samples_length, 80, args.latent_size, args.lr, args.alpha,
@@ -445,6 +461,17 @@ def main(argv=None):
         if world > 1:
             raise SystemExit("--gpu-loader 0 has no sharding: data-parallel runs feed from data.GpuPairLoader")
         loader, _ = get_dataset(args.dataset_fp, args.batch_size, args.samples_length, seed=args.seed, exclude=excluded)
+    if args.adv_weight is None and any(getattr(args, k) != get_parse().get_default(k) for k in ADV_KEYS):
+        raise SystemExit("--adv-hidden / --adv-lr / --adv-warmup-steps configure --adv-weight: give it too (a resume without "
+                         "any of the four restores the saved configuration)")
+    if args.adv_weight is not None:
+        if not args.train:
+            raise SystemExit("--adv-weight: the speaker adversary belongs to training (--train true)")
+        try:
+            vsc.set_speaker_adversary(args.adv_weight, n_speakers=len(loader.dataset.speaker_ids), hidden=args.adv_hidden,
+                                      lr=args.adv_lr, warmup_steps=args.adv_warmup_steps, seed=args.seed)
+        except ValueError as e:
+            raise SystemExit(f"--adv-weight: {e}")
     if args.graph:
         vsc.enable_graph(True)     # with a reducer attached the step still runs eagerly unless DVAE_DDP_GRAPH=1
     hist = None

@@ -48,7 +48,8 @@ extern "C" {
  * (dvae_latent_tables, dvae_latent_lse) were added at 319 without a new revision: the change is purely additive, no
  * existing argument list, structure or constant moved.  Likewise the scheduled loss (dvae_loss_fwd_sched,
  * dvae_loss_bwd_sched, dvae_loss_sched_t, DVAE_LOSS_MAX_D): additive, and the suites of the two earlier additions pin 319.
- * Likewise the latent map's four entry points (dvae_tsne_nn, dvae_tsne_affinities, dvae_tsne_forces, dvae_tsne_update). */
+ * Likewise the latent map's four entry points (dvae_tsne_nn, dvae_tsne_affinities, dvae_tsne_forces, dvae_tsne_update) and
+ * the speaker adversary's two (dvae_adv_rows, dvae_adv_params). */
 #define DVAE_ABI_VERSION 319
 int dvae_version(void);
 
@@ -903,6 +904,48 @@ int dvae_tsne_forces(const float* x, int64_t ld, int64_t N, int D, const float* 
                      const float* y, int want_kl, int64_t row0, int64_t nrows, float* rows, void* stream);
 int dvae_tsne_update(const float* rows, int64_t N, float* y, float* upd, float* gains, float lr, float momentum,
                      float exaggeration, double* kl, void* stream);
+
+/* ---- speaker adversary on the content latent (dvae_amd/adversary.py) ----
+ * The reference has the classifier and its loss (model/feature_selection.py:5-43, a speaker classifier with a cross-entropy
+ * loss) but never trains the encoder against it; this is the gradient-reversal remedy of Ganin & Lempitsky (2015), Chou et
+ * al. (2018) for voice conversion.  Added at 319 without a new revision: purely additive.
+ * The network is Linear(D, H) -> ReLU -> Linear(H, S) -> softmax cross-entropy over R rows, forward and backward in TWO
+ * launches.  x [R, ldx] fp32 is read in place (columns D .. ldx - 1 never; 4-byte alignment is enough); labels [R] int32;
+ * w1 [H, ldw1] (D <= ldw1 <= DVAE_ADV_MAX_D, ldw1 % 4 == 0, columns D .. ldw1 - 1 are padding: loaded with the row's 16-byte pieces, never used), b1 [H],
+ * w2 [S, H], b2 [S]; w1 and w2 16-byte aligned.  coef: DEVICE pointer to the reversal weight lambda; inv_rows = 1 / R.
+ * dvae_adv_rows, one workgroup per row r (all buffers dense: row_loss, row_pred [R]; h, g1 [R, H]; g2 [R, S]):
+ *     h[r, j]     = relu(sum_d w1[j, d] x[r, d] + b1[j])                   d ascending from +0, one fma per term, then the bias
+ *     logit_c     = sum_j w2[c, j] h[r, j] + b2[c]                         a wave per class: lane l adds the 16-byte pieces l,
+ *                   l + 64, ... of the row in ascending order (fma), the 64 lanes by the xor tree 32 .. 1, then the bias
+ *     row_loss[r] = logsumexp(logit) - logit[label]                        the row maximum taken off first (expf, logf)
+ *     row_pred[r] = arg-max of the logits, the lowest index on a tie
+ *     g2[r, c]    = inv_rows (softmax_c - onehot_c)                        softmax_c = expf(logit_c - max) * (1 / sum)
+ *     g1[r, j]    = h[r, j] > 0 ? sum_c g2[r, c] w2[c, j] : +0             c ascending from +0, one fma per term
+ *     dx[r, dx_col0 + d] = -(lambda * sum_j g1[r, j] w1[j, d])             eight runs of H / 8 consecutive j, each ascending (fma),
+ *                   added in run order; dx [R, lddx], lddx >= dx_col0 + D: every OTHER column of the row is written +0.0 (the
+ *                   gradient of a wider tensor whose columns dx_col0 .. dx_col0 + D - 1 are x; lddx = D, dx_col0 = 0: dense)
+ *   A row whose label is negative or >= S is IGNORED (dvae_softmax_ce's rule): row_loss 0, its rows of g2, g1 and dx +0.0, not
+ *   counted; h and row_pred are written all the same.  When the device value of lambda is exactly 0, dx is +0.0 everywhere
+ *   whatever the row holds: a NaN in the adversary does not reach the model while it only monitors.
+ * dvae_adv_params, one lane per element of dw2 [S, H], db2 [S], dw1 [H, ldw1], db1 [H]: the sum over the counted rows in
+ *   ascending order from +0 (fma), STORED, not accumulated:
+ *     dw2[c, j] = sum_r g2[r, c] h[r, j],  db2[c] = sum_r g2[r, c],  dw1[j, d] = sum_r g1[r, j] x[r, d],  db1[j] = sum_r g1[r, j]
+ *   padding columns of dw1 get +0.0.  The four may all be null (evaluation): then only `out` is written.  One more workgroup
+ *   writes out[4] = {sum of row_loss over the counted rows, counted rows, counted rows with row_pred == label,
+ *   out[0] * inv_rows}, added in float64 in row order by one thread.
+ * No atomics; every order is a function of (D, H, S) alone: a row's bits do not depend on the other rows, and two launches
+ * give the same bits.  Null required pointers, R < 1, D outside 1 .. DVAE_ADV_MAX_D, H outside 64 .. DVAE_ADV_MAX_H or not a
+ * multiple of 64, S outside 1 .. DVAE_CE_MAX_CLASSES, ldx < D, a bad ldw1, dx_col0 < 0, lddx < dx_col0 + D, a misaligned w1 /
+ * w2, or some but not all of the four gradients null return DVAE_EINVAL and launch nothing. */
+#define DVAE_ADV_MAX_D 64
+#define DVAE_ADV_MAX_H 1024
+int dvae_adv_rows(const float* x, int64_t ldx, const int* labels, const float* w1, int ldw1, const float* b1,
+                  const float* w2, const float* b2, const float* coef, float inv_rows, int R, int D, int H, int S,
+                  float* row_loss, int* row_pred, float* h, float* g2, float* g1, float* dx, int64_t lddx, int dx_col0,
+                  void* stream);
+int dvae_adv_params(const float* x, int64_t ldx, const int* labels, const float* h, const float* g2, const float* g1,
+                    const float* row_loss, const int* row_pred, float inv_rows, int R, int D, int H, int S, float* dw1,
+                    int ldw1, float* db1, float* dw2, float* db2, float* out, void* stream);
 
 /* ---- held-out validation (model/variational_base_vae.py: validate) ----
  * The reference's test() (variational_base_vae.py:105-123) sums loss_functionGVAE2 (disentangled_vae.py:310-327) over the
