@@ -116,7 +116,8 @@ __device__ __forceinline__ void lstm_pack_bf16(const float* __restrict__ W, __bf
 }
 
 // fp32x3 fragment packing: as the bf16 packing with THREE planes per (chunk, lane): w = p0 + p1 + p2 exactly (two
-// round-to-nearest splits, the last residual is exact in bf16).  [..][kc][plane][lane][8]
+// round-to-nearest splits, the last residual is exact in bf16 — for |w| >= 2^-110; below, see dvae_lstm_pack_w_x3 in
+// include/dvae_hip.h).  [..][kc][plane][lane][8]
 __device__ __forceinline__ void split3_scalar(float x, __bf16& a, __bf16& b, __bf16& c) {
   a = (__bf16)x;
   const float r1 = x - (float)a;
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(256) void lstm_pack_w_bf16_kernel(const float* __re
 __global__ __launch_bounds__(256) void repack_all_kernel(const Table t) {
   __shared__ float tile[32][33];
   int di = 0;
-  while (di + 1 < t.n && (int)blockIdx.x >= t.blk_begin[di + 1]) ++di;   // uniform scan, n <= 56
+  while (di + 1 < t.n && (int)blockIdx.x >= t.blk_begin[di + 1]) ++di;   // uniform scan, n <= MAX_DESC
   const Desc& d = t.d[di];
   const int lb = blockIdx.x - t.blk_begin[di], nb = t.blk_begin[di + 1] - t.blk_begin[di];
   switch (d.kind) {
@@ -226,10 +227,16 @@ __global__ __launch_bounds__(256) void repack_all_kernel(const Table t) {
   }
 }
 
+// the packs move whole 16-byte vectors on both sides
+inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
+}
+
 }  // namespace
 
 DVAE_API int dvae_lstm_pack_w(const float* w_hh, float* packed_fwd, float* packed_bwd, int H, void* stream) {
   if (!w_hh || (!packed_fwd && !packed_bwd) || H < 64 || (H & 63)) return DVAE_EINVAL;
+  if (!aligned16(w_hh, packed_fwd, packed_bwd)) return DVAE_EINVAL;
   const int64_t total = (int64_t)4 * (H / 16) * (H / 16) * 64;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
@@ -239,6 +246,7 @@ DVAE_API int dvae_lstm_pack_w(const float* w_hh, float* packed_fwd, float* packe
 
 DVAE_API int dvae_lstm_pack_w_bf16(const float* w_hh, void* packed_fwd, void* packed_bwd, int H, void* stream) {
   if (!w_hh || (!packed_fwd && !packed_bwd) || H < 512 || (H % 512)) return DVAE_EINVAL;
+  if (!aligned16(w_hh, packed_fwd, packed_bwd)) return DVAE_EINVAL;
   const int64_t total = (int64_t)4 * (H / 16) * (H / 32) * 64;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
@@ -249,6 +257,7 @@ DVAE_API int dvae_lstm_pack_w_bf16(const float* w_hh, void* packed_fwd, void* pa
 
 DVAE_API int dvae_lstm_pack_w_x3(const float* w_hh, void* packed_fwd, void* packed_bwd, int H, void* stream) {
   if (!w_hh || (!packed_fwd && !packed_bwd) || H < 512 || (H % 512)) return DVAE_EINVAL;
+  if (!aligned16(w_hh, packed_fwd, packed_bwd)) return DVAE_EINVAL;
   const int64_t total = (int64_t)4 * (H / 16) * (H / 32) * 64;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
@@ -272,6 +281,7 @@ DVAE_API int dvae_repack_all(const dvae_repack_desc_t* descs, int n, void* strea
         break;
       case DVAE_REPACK_LSTM_PACK:
         if (!s.src || (!s.dst && !s.dst2) || s.d0 < 64 || (s.d0 & 63)) return DVAE_EINVAL;
+        if (!aligned16(s.src, s.dst, s.dst2)) return DVAE_EINVAL;
         for (int m : {s.d1, s.d2})
           if ((m != DVAE_MODE_F32 && m != DVAE_MODE_BF16 && m != DVAE_MODE_F32X3) || (m != DVAE_MODE_F32 && (s.d0 % 512)))
             return DVAE_EINVAL;
@@ -290,7 +300,9 @@ DVAE_API int dvae_repack_all(const dvae_repack_desc_t* descs, int n, void* strea
         elems = s.d0;
         break;
       case DVAE_REPACK_CAST_BF16:
-        if (!s.src || !s.dst || s.d0 < 1 || s.d1 < 1 || (((int64_t)s.d0 * s.d1) & 3)) return DVAE_EINVAL;
+        if (!s.src || !s.dst || s.d0 < 1 || s.d1 < 1 || (((int64_t)s.d0 * s.d1) & 3) || (((uintptr_t)s.src) & 15) ||
+            (((uintptr_t)s.dst) & 7))   // f32x4 loads, bf16x4 stores
+          return DVAE_EINVAL;
         elems = (int64_t)s.d0 * s.d1;
         break;
       default:

@@ -264,11 +264,19 @@ typedef struct {
                          every direction of a call must name the same stride */
 } dvae_lstm_dir_t;
 #define DVAE_PERS_BIAS_SLABS 16  /* rows of dvae_lstm_dir_t.dbias_part */
-/* W_hh [4H,H] -> fragment-ordered copies (each 4H*H floats) for the forward / backward frame kernels */
+/* W_hh [4H,H] -> fragment-ordered copies (each 4H*H floats) for the forward / backward frame kernels.  All three pack
+ * entry points move 16-byte vectors: w_hh and every pack given must be 16-byte aligned (DVAE_EINVAL otherwise). */
 int dvae_lstm_pack_w(const float* w_hh, float* packed_fwd, float* packed_bwd, int H, void* stream);
 /* bf16 compute mode: the same copies rounded to bf16 (each 4H*H bf16 values = 2*4H*H bytes) */
 int dvae_lstm_pack_w_bf16(const float* w_hh, void* packed_fwd, void* packed_bwd, int H, void* stream);
-/* fp32x3 mode: three bf16 planes per fragment, w == w1 + w2 + w3 exactly (each copy 3 * 4H*H bf16 values = 6*4H*H bytes) */
+/* fp32x3 mode: three bf16 planes per fragment, [..][kc][plane][lane][8] with w1 = rne(w), w2 = rne(w - w1),
+ * w3 = w - w1 - w2, so w == w1 + w2 + w3 exactly (each copy 3 * 4H*H bf16 values = 6*4H*H bytes).  "Exactly" holds for
+ * 2^-110 <= |w| (and 0): the last bit of w3 lies 23 binary places below w's exponent, and bf16 ends at 2^-133.
+ * Below that it does NOT hold in general.  Nothing is flushed: on the MI355X the pack of fp32 SUBNORMAL weights is bit for
+ * bit the IEEE split (tests/test_hip_repack.py::test_x3_pack_of_subnormal_weights_is_finite prints it) — w1 = rne(w) on
+ * bf16's subnormal grid (multiples of 2^-133), w2 = w3 = 0 (the residual is at most half a step of that grid and rounds to
+ * zero), so the planes sum to rne(w), which equals w only for the 1 in 65 536 weights that lie on the grid.  Every plane
+ * stays finite. */
 int dvae_lstm_pack_w_x3(const float* w_hh, void* packed_fwd, void* packed_bwd, int H, void* stream);
 /* ---- all weight-derived operand layouts of a model in ONE launch (once per training step, after Adam) ----
  * kind CONV_T    src Wp[5][d0=Cout][d1=Cin]                 -> dst Wpt[5][Cin][Cout]  (operand of dvae_conv5_dgrad_t)
@@ -279,10 +287,18 @@ int dvae_lstm_pack_w_x3(const float* w_hh, void* packed_fwd, void* packed_bwd, i
  *      TRANSPOSE src W[d0][d1]                              -> dst W^T[d1][d0]         (bf16 destination when d2 & 1;
  *                                                                                       CONV_T likewise); d2 >> 1 = row
  *                                                                                       stride of dst in elements (0: d0)
- *      COPY_F32  src [d0] fp32                              -> dst, same layout        (weights of two directions side by side)
- *      ADD2      src, src2 [d0]                             -> dst = src + src2        (b_ih + b_hh)
- *      CAST_BF16 src [d0*d1] fp32                           -> dst bf16, same layout   (bf16 mode: weight operands)
- * `descs` is a HOST array of n <= 72 entries (copied into the launch); the device buffers are the caller's. */
+ *      COPY_F32  src [d0] fp32, d0 % 4 == 0                 -> dst, same layout, the same bits (weights of two directions
+ *                                                              side by side)
+ *      ADD2      src, src2 [d0]                             -> dst = src + src2        (b_ih + b_hh; dst may be src)
+ *      CAST_BF16 src [d0*d1] fp32, d0*d1 % 4 == 0           -> dst bf16, same layout, rounded to nearest even
+ *                                                              (bf16 mode: weight operands)
+ * CONV_T and TRANSPOSE write exactly the d0*d1 (five times that) elements named: with a row stride above d0 the columns
+ * between the rows keep what they held.  A bf16 destination is rounded to nearest even.
+ * Alignment (these kinds move whole vectors; DVAE_EINVAL otherwise, as for every other bad field, and nothing is launched):
+ * COPY_F32 src and dst 16 bytes; CAST_BF16 src 16 bytes, dst 8 bytes; LSTM_PACK src, dst and dst2 16 bytes.  CONV_T,
+ * TRANSPOSE and ADD2 go element by element and take any fp32 / bf16 aligned address.
+ * `descs` is a HOST array of 1 <= n <= 72 entries (copied into the launch); the device buffers are the caller's.  A
+ * descriptor is worked on by ceil(elements / 8192) workgroups, at most 512. */
 #define DVAE_REPACK_CONV_T 0
 #define DVAE_REPACK_LSTM_PACK 1
 #define DVAE_REPACK_TRANSPOSE 2
