@@ -59,6 +59,8 @@ class LossSched(C.Structure):
 
 
 LOSS_MAX_D = 1024         # DVAE_LOSS_MAX_D
+LATENT_MAX_D = 64         # DVAE_LATENT_MAX_D
+FACTOR_MAX_N = 1024       # DVAE_FACTOR_MAX_N
 
 REPACK_CONV_T, REPACK_LSTM_PACK, REPACK_TRANSPOSE, REPACK_ADD2, REPACK_CAST_BF16, REPACK_COPY_F32 = 0, 1, 2, 3, 4, 5
 
@@ -193,6 +195,9 @@ SIGNATURES = {
     "dvae_adv_rows": (i32, [vp, i64, vp, vp, i32, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, i32,
                             vp]),
     "dvae_adv_params": (i32, [vp, i64, vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp]),
+    "dvae_factor_ws_bytes": (i64, [i32]),
+    "dvae_factor_fwd": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "dvae_factor_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "dvae_pair_metrics": (i32, [vp] * 9 + [i32, i64, i32, i32, f32, f32, vp]),
     "dvae_group_sum_f64": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "dvae_prof_enable": (i32, [i32]),

@@ -459,3 +459,4 @@ DVAE_API int dvae_gmm_score(const float* x, int64_t ldx, int col0, int D, const 
 #include "latents.hip"      // the latent report: part of this translation unit
 #include "tsne.hip"         // the latent map: the same
 #include "adversary.hip"    // the speaker adversary: the same
+#include "factor.hip"       // the total-correlation / shared-information penalty: the same

@@ -239,6 +239,9 @@ class DisentangledVAE(nn.Module):
         # explicit reparameterisation noise for parity runs: (eps_content1, eps_content2, eps_style),
         # the reference's three normal_() draws in call order (disentangled_vae.py:252,255,261)
         self.eps_override: Optional[Sequence[torch.Tensor]] = None
+        # True: forward_full(train=True) leaves aliases of (z, q_mu, q_lv) in `factor_inputs` for the trainer's factor penalty
+        self.factor_tap = False
+        self.factor_inputs = None
 
     # ---- parameters in the order their gradients complete during backward (for bucketed all-reduce)
     def backward_param_order(self):
@@ -436,6 +439,14 @@ class DisentangledVAE(nn.Module):
         else:
             eps_c, eps_s = None, eps_style.to(x1.device, torch.float32).contiguous()
         z, q_mu, q_lv, s_mu, s_lv = LatentFn.apply(style, content, eps_c, eps_s, Bh, S, Cn)
+        self.factor_inputs = None
+        if self.factor_tap and train:
+            # the factor penalty (ConvolutionalMulVAE.set_factor_penalty) is a second consumer of z, q_mu and q_lv: the trainer
+            # applies it to these aliases, and each pair of gradients is summed by one launch (ops.FanoutFn)
+            z, z_f = fanout(z, 2)
+            q_mu, q_mu_f = fanout(q_mu, 2)
+            q_lv, q_lv_f = fanout(q_lv, 2)
+            self.factor_inputs = (z_f, q_mu_f, q_lv_f)
         y = self._decode_frames(z, T, N, 2)                              # [T*N, 80]
         y, y_res, y_in = fanout(y, 3)       # loss, residual and postnet input: one gradient sum (ops.FanoutFn)
         y_hat = self.postnet.forward_frames(y_in, N, 2, residual=y_res,  # y + postnet(y)
@@ -595,6 +606,52 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         self.adv_config = cfg
         self._adv_sent, self._adv_k, self.adv_weight = None, None, None
         self.adv_out = self.adv_pred = self.adv_stats = None
+
+    def set_factor_penalty(self, tc_weight=None, shared_weight=0.0, *, warmup_steps=0):
+        """The beta-TCVAE penalty (Chen et al. 2018) on the minibatch of every TRAINING step, inside the replayed graph
+        (ops.FactorPenaltyFn, csrc/factor.hip): LOSS + tc_weight (tc_style + tc_content) +
+        shared_weight shared, the estimator of `python -m dvae_amd.latents` on the 2 Bh rows of the step, in nats per row.
+        tc_weight: None (off: the step launches what it launched without this, under the same graph signature) or >= 0;
+        (0, 0) is a live monitor: the statistics are computed, the model's step keeps its bits.  With both weights beta - 1 the
+        penalty is beta-TCVAE's.  The effective weights at the optimiser's step count k are w min(1, k / warmup_steps): two
+        device scalars refreshed by one small copy before the step, never a new capture.  The eight reported scalars, LOSS
+        included, stay the reference's; `factor_aux` (float[5] on the device: tc_style, tc_content, shared, mi, penalty) holds
+        the statistics of the last step and `train()` reports their means as Factor/... in `factor_stats`.  Validation,
+        `Val/Loss` and checkpoints/best.json do not see the penalty: epochs stay compared under one fixed objective.
+        Data parallel: every rank penalises its LOCAL rows and computes the same weights from the same step count; nothing is
+        exchanged (not run on more than one GPU)."""
+        opt = self.optimizer
+        if tc_weight is None:
+            self.factor_cfg = None
+            self.model.factor_tap = False
+            opt.factor_penalty = None
+            return
+        try:
+            tc_weight, shared_weight, warmup_steps = float(tc_weight), float(shared_weight), int(warmup_steps)
+        except (TypeError, ValueError):
+            raise ValueError("set_factor_penalty: tc_weight and shared_weight are numbers, warmup_steps an integer")
+        if not (tc_weight >= 0.0 and math.isfinite(tc_weight) and shared_weight >= 0.0 and math.isfinite(shared_weight)) \
+                or warmup_steps < 0:
+            raise ValueError(f"set_factor_penalty: tc_weight {tc_weight} and shared_weight {shared_weight} must be finite and "
+                             f">= 0, warmup_steps {warmup_steps} >= 0")
+        D = self.model.latent_dim
+        if D > _lib.LATENT_MAX_D:
+            raise ValueError(f"set_factor_penalty: {D} latent dimensions, the penalty's kernels take {_lib.LATENT_MAX_D}")
+        if 2 * int(self.batch_size) > _lib.FACTOR_MAX_N:
+            raise ValueError(f"set_factor_penalty: {2 * int(self.batch_size)} rows per step, the penalty's kernels take "
+                             f"{_lib.FACTOR_MAX_N}")
+        dev = opt.flat_p.device
+        if dev.type != "cuda":
+            raise RuntimeError("set_factor_penalty: the penalty runs only on the HIP device (no CPU fallback)")
+        if getattr(self, "_fac_coef", None) is None:        # allocated once: a captured graph holds their addresses
+            self._fac_coef = torch.zeros(2, device=dev, dtype=torch.float32)
+            self.factor_aux = torch.zeros(5, device=dev, dtype=torch.float32)
+            self._fac_pin, self._fac_pin_ev, self._fac_pin_i = None, None, 0
+        self.factor_cfg = dict(tc_weight=tc_weight, shared_weight=shared_weight, warmup_steps=warmup_steps)
+        self.model.factor_tap = True
+        opt.factor_penalty = dict(self.factor_cfg)      # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
+        self._fac_sent, self._fac_k, self.factor_weights = None, None, None
+        self.factor_stats = None
 
     def kl_weight_at(self, k, epoch=1):
         """The KL weight of the step that runs after `k` optimiser steps, in epoch `epoch` (kl_schedule.KLSchedule)."""

@@ -118,13 +118,51 @@ class VariationalBaseModelVAE:
         return (tuple(data1.shape), tuple(opt.betas), float(opt.eps)) + cofs + (
                 int(self.batch_size), bool(self.model.training),
                 self.reducer is not None, getattr(self.reducer, "world_size", 1), ops.current_mode(),
-                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature() + kl + self._adv_signature()
+                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature() + kl + self._adv_signature() \
+            + self._factor_signature()
 
     def _adv_signature(self):
         """The speaker adversary on/off and its shape change the launches of a step; its weight does not (a device scalar,
         _sync_adv_coef).  Nothing is added while it is off."""
         adv = getattr(self, "adversary", None)
         return (("adv", adv.hidden, adv.n_speakers),) if adv is not None else ()
+
+    def _factor_signature(self):
+        """The factor penalty on/off changes the launches of a step; its two weights and their warm-up do not (device scalars,
+        _sync_factor_coef).  Nothing is added while it is off."""
+        return (("factor",),) if getattr(self, "factor_cfg", None) is not None else ()
+
+    def factor_weights_at(self, k):
+        """(w_tc, w_sh) of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
+        cfg = self.factor_cfg
+        n = int(cfg["warmup_steps"])
+        f = 1.0 if n <= 0 else min(1.0, k / n)
+        return float(cfg["tc_weight"]) * f, float(cfg["shared_weight"]) * f
+
+    def _sync_factor_coef(self):
+        """Host -> device copy of the penalty's two weights for the step about to run when they changed since the last copy;
+        beside _sync_kl_coef and _sync_adv_coef, never inside a capture.  The step's number is the optimiser's step count,
+        kept by the host as `_fac_k` exactly as `_kl_k` is."""
+        if getattr(self, "factor_cfg", None) is None:
+            return
+        if self._fac_k is None:
+            self._fac_k = self.optimizer.t
+        pair = self.factor_weights_at(self._fac_k)
+        if pair != self._fac_sent:
+            if self._fac_pin is None:
+                self._fac_pin = torch.empty(16, 2, dtype=torch.float32, pin_memory=True)
+                self._fac_pin_ev = [None] * 16
+            i = self._fac_pin_i = (self._fac_pin_i + 1) % 16
+            if self._fac_pin_ev[i] is not None:
+                self._fac_pin_ev[i].synchronize()
+            self._fac_pin[i, 0], self._fac_pin[i, 1] = pair
+            self._fac_coef[0:2].copy_(self._fac_pin[i], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._fac_pin_ev[i] = ev
+            self._fac_sent = pair
+        self.factor_weights = pair
+        self._fac_k += 1
 
     def adv_weight_at(self, k):
         """The reversal weight of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
@@ -230,6 +268,7 @@ class VariationalBaseModelVAE:
             self._sync_kl_coef()
             self._sync_adv_guard()
             self._sync_adv_coef()       # likewise the adversary's reversal weight
+            self._sync_factor_coef()    # ... and the factor penalty's two weights
         return self._train_step_body(data1, data2, labels2)
 
     def _sync_adv_guard(self):
@@ -256,6 +295,9 @@ class VariationalBaseModelVAE:
             if self.reducer is not None:
                 raise ValueError("the speaker adversary is not trained data parallel")
             adv.optimizer.zero_grad()       # store-first parameters only: no launch, the written-once counts start over
+        fac = getattr(self, "factor_cfg", None)
+        if fac is not None and not (hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full")):
+            raise RuntimeError("the factor penalty needs the unsplit forward (forward_full / losses_vector_full)")
         if hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full"):
             # the eight scalars as one vector (fused loss kernels) on the UNSPLIT outputs; backward is seeded with the
             # constant (1, 0, ..., 0): `vec[0].backward()` and the reference's ten output slices cost ~25 zero-fill /
@@ -272,6 +314,16 @@ class VariationalBaseModelVAE:
             if getattr(self, "_loss_seed", None) is None or self._loss_seed.device != vec.device:
                 self._loss_seed = torch.zeros(8, device=vec.device)
                 self._loss_seed[0] = 1.0
+            roots, seeds = [vec], [self._loss_seed]
+            if fac is not None:
+                # LOSS + penalty: the penalty reads the aliases forward_full left of (z, q_mu, q_lv) and the two weights on the
+                # device; ONE backward adds its three gradients to the decoder's and the loss's (ops.FanoutFn: one sum each)
+                from .. import ops
+                pen = ops.FactorPenaltyFn.apply(*self.model.factor_inputs, self.model.speaker_size, self._fac_coef,
+                                                self.factor_aux)
+                self.model.factor_inputs = None
+                roots.append(pen)
+                seeds.append(ops.unit_seed(vec.device))
             if adv is not None:
                 # q_mu [2 Bh, S + Cn]: the content means are its columns S .. S + Cn - 1; both launches run here, the
                 # classifier's gradients land in its optimiser's buffer, and ONE backward adds the reversed gradient of
@@ -280,7 +332,10 @@ class VariationalBaseModelVAE:
                 stats = {}
                 ce = adv.loss(outs[2], labels2, self._adv_coef, self.model.speaker_size, stats)
                 self.adv_out, self.adv_pred = stats["out"], stats["row_pred"]
-                torch.autograd.backward([vec, ce], [self._loss_seed, ops.unit_seed(vec.device)])
+                roots.append(ce)
+                seeds.append(ops.unit_seed(vec.device))
+            if len(roots) > 1:
+                torch.autograd.backward(roots, seeds)
             else:
                 torch.autograd.backward(vec, self._loss_seed)
         else:
@@ -335,6 +390,10 @@ class VariationalBaseModelVAE:
             self._sync_adv_guard()      # ... as are the buffers of the adversary's non-finite guard
             adv.optimizer.sync_scalars(1.0)
             self._sync_adv_coef()       # ... and the adversary's reversal weight
+        if getattr(self, "factor_cfg", None) is not None:
+            from .. import ops
+            ops.unit_seed(dev)          # allocated outside the capture
+            self._sync_factor_coef()    # the factor penalty's two weights (nothing while it is off)
         if self._graph is not None and not getattr(self.optimizer, "_clean", True):
             # something accumulated into the gradient buffer since the last Adam launch (a manual backward between two
             # replays): a graph captured on a clean buffer holds no zero_grad launch of its own
@@ -392,13 +451,16 @@ class VariationalBaseModelVAE:
 
     # ---- variational_base_vae.py:58-70
     def step(self, data1, data2, speaker_ids, train=False):
-        if train and (getattr(self, "kl_sched", None) is not None or getattr(self, "adversary", None) is not None):
+        if train and (getattr(self, "kl_sched", None) is not None or getattr(self, "adversary", None) is not None
+                      or getattr(self, "factor_cfg", None) is not None):
             # the same one copy carries the optimiser's step count: the schedule's position is exactly t (a skipped step)
             vec = torch.cat([self.step_async(data1, data2, speaker_ids), self.optimizer.dev_state[0:1]]).tolist()
             if getattr(self, "kl_sched", None) is not None:
                 self._kl_k = int(vec[8])
             if getattr(self, "adversary", None) is not None:
                 self._adv_k = int(vec[8])
+            if getattr(self, "factor_cfg", None) is not None:
+                self._fac_k = int(vec[8])
             self._check_and_recover()
             return tuple(vec[:8])
         if train:
@@ -459,6 +521,12 @@ class VariationalBaseModelVAE:
         self.adv_stats = None
         if adv is not None:
             asum = torch.zeros(4, dtype=torch.float64, device=self.device)
+        # the factor penalty on (set_factor_penalty): its five statistics of every step join a running float64 tensor
+        fac = getattr(self, "factor_cfg", None)
+        self.factor_stats = None
+        if fac is not None:
+            fsum = torch.zeros(5, dtype=torch.float64, device=self.device)
+            fsteps = 0
         for data1, data2, speaker_ids in train_loader:
             data1 = data1.to(self.device, non_blocking=True).float()
             data2 = data2.to(self.device, non_blocking=True).float()
@@ -467,6 +535,9 @@ class VariationalBaseModelVAE:
             tot.add_(last)
             if adv is not None:
                 asum.add_(self.adv_out)
+            if fac is not None:
+                fsum.add_(self.factor_aux)
+                fsteps += 1
             if sched is not None:
                 ksum.add_(self.kl_aux[2:4 + 2 * kD])
                 ksteps += 1
@@ -482,6 +553,15 @@ class VariationalBaseModelVAE:
             self.adv_stats = {"Adv/CE": a[0] / a[1] if a[1] else float("nan"),
                               "Adv/Accuracy": a[2] / a[1] if a[1] else float("nan"),
                               "Adv/Weight": self.adv_weight if self.adv_weight is not None else self.adv_weight_at(self._adv_k)}
+        if fac is not None:
+            # likewise: the five sums, and the optimiser's step count to set the warm-up's position right
+            f = torch.cat([fsum, opt.dev_state[0:1].double()]).tolist()
+            self._fac_k = int(f[5])
+            n = max(1, fsteps)
+            w = self.factor_weights if self.factor_weights is not None else self.factor_weights_at(self._fac_k)
+            self.factor_stats = {"Factor/TC style": f[0] / n, "Factor/TC content": f[1] / n, "Factor/Shared": f[2] / n,
+                                 "Factor/MI": f[3] / n, "Factor/Penalty": f[4] / n, "Factor/Weight tc": w[0],
+                                 "Factor/Weight shared": w[1]}
         ktail = []
         if sched is not None:
             tot = torch.cat([tot, ksum, opt.dev_state[0:1].double()])     # behind the eight sums, in front of the rest
@@ -667,6 +747,12 @@ class VariationalBaseModelVAE:
                 self.set_kl_schedule(saved["kind"], **{k: saved[k] for k in ("start", "steps", "cycles", "ratio", "free_bits")})
             if getattr(self, "kl_sched", None) is not None:
                 self._kl_k = None
+            # likewise the factor penalty (load_state_dict has refused a different one)
+            saved = sd.get("factor_penalty")
+            if saved is not None and getattr(self, "factor_cfg", None) is None and hasattr(self, "set_factor_penalty"):
+                self.set_factor_penalty(saved["tc_weight"], saved["shared_weight"], warmup_steps=saved["warmup_steps"])
+            if getattr(self, "factor_cfg", None) is not None:
+                self._fac_k = None
             if sd.get("cuda_rng_state") is not None and torch.device(self.device).type == "cuda":
                 g = torch.cuda.default_generators[torch.device(self.device).index or 0]
                 if self.reducer is not None and self.reducer.rank > 0:
@@ -839,6 +925,8 @@ class VariationalBaseModelVAE:
                 rec.update(self.ema_stats)
             if getattr(self, "adv_stats", None):        # speaker adversary on (set_speaker_adversary)
                 rec.update(self.adv_stats)
+            if getattr(self, "factor_stats", None):     # factor penalty on (set_factor_penalty)
+                rec.update(self.factor_stats)
             if getattr(self, "kl_stats", None):         # KL schedule on (set_kl_schedule)
                 rec.update(self.kl_stats)
                 if logs_path and self._is_rank0():

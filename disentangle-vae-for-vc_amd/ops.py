@@ -1753,6 +1753,52 @@ class SpeakerAdversaryFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None, None, None
 
 
+# ----------------------------------------------------------------------------- factor penalty (csrc/factor.hip)
+class FactorPenaltyFn(torch.autograd.Function):
+    """The total-correlation / shared-information penalty of Chen et al. (2018) on the N = 2 Bh rows of a training step
+    (DESIGN.md section 4.19): weights[0] (tc_style + tc_content) + weights[1] shared, a device scalar, from z, q_mu, q_lv
+    [N, S + Cn] as ops.LatentFn leaves them.  `weights` (float[2] on the device: w_tc, w_sh with the warm-up applied) and
+    `stats` (float[5]: tc_style, tc_content, shared, mi, penalty) belong to the CALLER: a captured graph holds their
+    addresses, the trainer refreshes the one before a step and adds the other up after it.  Two launches forward
+    (dvae_factor_fwd), one backward (dvae_factor_bwd: dz from the workgroups that own a row, dq_mu and dq_lv from those that
+    own a column); with both device weights 0 the three gradients are +0.0 whatever the inputs hold."""
+
+    @staticmethod
+    def forward(ctx, z, q_mu, q_lv, S, weights, stats):
+        z, q_mu, q_lv = z.contiguous(), q_mu.contiguous(), q_lv.contiguous()
+        _ok(z, q_mu, q_lv, weights, stats)
+        S = int(S)
+        if z.dim() != 2 or q_mu.shape != z.shape or q_lv.shape != z.shape:
+            raise ValueError("factor penalty: z, q_mu and q_lv are [N, D] tensors of one shape")
+        N, D = z.shape
+        if not (1 <= N <= _lib.FACTOR_MAX_N and S >= 1 and D - S >= 1 and D <= _lib.LATENT_MAX_D):
+            raise ValueError(f"factor penalty: N = {N} rows (1 .. {_lib.FACTOR_MAX_N}), {S} style and {D - S} content "
+                             f"dimensions (>= 1 each, {_lib.LATENT_MAX_D} together at most)")
+        if not (weights.is_contiguous() and weights.numel() >= 2 and stats.is_contiguous() and stats.numel() >= 5):
+            raise ValueError("factor penalty: weights is a contiguous float[2], stats a contiguous float[5]")
+        Lib = lib()
+        dev = z.device
+        L = torch.empty((N, D + 3), device=dev, dtype=torch.float32)
+        ws = torch.empty((Lib.dvae_factor_ws_bytes(N) // 4,), device=dev, dtype=torch.float32)
+        pen = torch.empty((), device=dev, dtype=torch.float32)
+        check(Lib.dvae_factor_fwd(ptr(z), ptr(q_mu), ptr(q_lv), N, D, S, ptr(weights), ptr(L), ptr(stats), ptr(pen), ptr(ws),
+                                  stream()), "dvae_factor_fwd")
+        ctx.save_for_backward(z, q_mu, q_lv, L, weights)
+        ctx.S = S
+        return pen
+
+    @staticmethod
+    def backward(ctx, g):
+        z, q_mu, q_lv, L, weights = ctx.saved_tensors
+        g = g.contiguous()
+        _ok(g)
+        N, D = z.shape
+        dz, dmu, dlv = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
+        check(lib().dvae_factor_bwd(ptr(z), ptr(q_mu), ptr(q_lv), ptr(L), N, D, ctx.S, ptr(weights), ptr(g), ptr(dz),
+                                    ptr(dmu), ptr(dlv), stream()), "dvae_factor_bwd")
+        return dz, dmu, dlv, None, None, None
+
+
 def prof_enable(family: int):
     check(lib().dvae_prof_enable(family), "dvae_prof_enable")
 

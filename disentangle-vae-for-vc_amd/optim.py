@@ -96,6 +96,9 @@ class FlatAdam:
         # the KL schedule the trainer runs under (ConvolutionalMulVAE.set_kl_schedule: its parameters as plain numbers, or
         # None): kept here because its position IS the step count `t`, and so that it rides in state_dict()
         self.kl_schedule = None
+        # likewise the factor penalty's configuration (ConvolutionalMulVAE.set_factor_penalty), or None: its warm-up's
+        # position is the step count too
+        self.factor_penalty = None
         # True: the zero_grad ranges of flat_g are known to be zero (the last Adam launch cleared them after reading and no
         # backward kernel has accumulated since: ops._grad_buf resets it) — zero_grad() is then free
         self._clean = False
@@ -423,6 +426,8 @@ class FlatAdam:
                          "avg": {n: self._to_ref(n, v).detach().cpu().contiguous() for n, v in self._ema_views()}}
         if self.kl_schedule is not None:
             sd["kl_schedule"] = dict(self.kl_schedule)
+        if self.factor_penalty is not None:
+            sd["factor_penalty"] = dict(self.factor_penalty)
         return sd
 
     def load_state_dict(self, sd, legacy_layout=None):
@@ -433,6 +438,11 @@ class FlatAdam:
         if saved_kl is not None and self.kl_schedule is not None and dict(saved_kl) != dict(self.kl_schedule):
             raise ValueError(f"optimizer state was trained under the KL schedule {dict(saved_kl)}, this run asks for "
                              f"{dict(self.kl_schedule)}: resume with the same schedule (or with none: the saved one is "
+                             "restored), or start a new run")
+        saved_fac = sd.get("factor_penalty")
+        if saved_fac is not None and self.factor_penalty is not None and dict(saved_fac) != dict(self.factor_penalty):
+            raise ValueError(f"optimizer state was trained under the factor penalty {dict(saved_fac)}, this run asks for "
+                             f"{dict(self.factor_penalty)}: resume with the same penalty (or with none: the saved one is "
                              "restored), or start a new run")
         fmt = int(sd.get("format", 1))
         if fmt == 1:

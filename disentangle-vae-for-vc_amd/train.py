@@ -20,6 +20,10 @@ scalars.jsonl, <log_dir>/kl_dims.json; the schedule rides in the .opt sidecar an
 reaches the encoder reversed and scaled by F (ConvolutionalMulVAE.set_speaker_adversary, adversary.py; 0: it only monitors);
 --adv-hidden, --adv-lr, --adv-warmup-steps; Adv/... in scalars.jsonl; it is checkpointed as <name>_<epoch>.adv.pth beside the
 .pth, and a resume continues it (without the flags: with the saved configuration).
+--tc-weight F [--shared-weight F] [--factor-warmup-steps N] (new, opt-in): the beta-TCVAE penalty on the minibatch of every
+training step, inside the replayed step (ConvolutionalMulVAE.set_factor_penalty, csrc/factor.hip): F times the total correlation
+inside the style and inside the content block, --shared-weight times the information the two blocks share; --tc-weight 0 alone
+only monitors; Factor/... in scalars.jsonl; the configuration rides in the .opt sidecar and a resume continues it.
 --convert (reference variational_base_vae.py:243-330, minus plots): the first --convert-count sorted utterances of
 --src_spk, each with a random utterance of --trg_spk (seeded by --seed), through `convert_mel`; the converted mels are
 voiced by the GPU Griffin-Lim inverse of the mel front-end (frontend.MelInverter, --griffin-lim-iters) instead of the
@@ -132,9 +136,19 @@ def get_parse():
     p.add_argument("--adv-lr", type=float, default=1e-3, help="--adv-weight: learning rate of the classifier's own Adam")
     p.add_argument("--adv-warmup-steps", type=int, default=0,
                    help="--adv-weight: the weight rises linearly from 0 over this many optimiser steps")
+    p.add_argument("--tc-weight", type=float, default=None,
+                   help="penalise the total correlation inside the style and inside the content block on the minibatch of every "
+                        "training step, with this weight, in nats per row (0 without --shared-weight: the statistics are "
+                        "computed, the model is untouched: a monitor).  Default: off")
+    p.add_argument("--shared-weight", type=float, default=None,
+                   help="penalise the information the style and the content block share, with this weight; alone it implies "
+                        "--tc-weight 0")
+    p.add_argument("--factor-warmup-steps", type=int, default=0,
+                   help="--tc-weight / --shared-weight: both weights rise linearly from 0 over this many optimiser steps")
     return p
 
 
+FACTOR_KEYS = ("tc_weight", "shared_weight", "factor_warmup_steps")
 ADV_KEYS = ("adv_weight", "adv_hidden", "adv_lr", "adv_warmup_steps")
 KL_KEYS = ("kl_schedule", "kl_start", "kl_warmup_steps", "kl_cycles", "kl_ratio", "free_bits", "free_bits_style",
            "free_bits_content")
@@ -423,6 +437,9 @@ def main(argv=None):
         if all(cfg[k] == get_parse().get_default(k) for k in ADV_KEYS):
             for k in ADV_KEYS:      # likewise the flags of the speaker adversary
                 del cfg[k]
+        if all(cfg[k] == get_parse().get_default(k) for k in FACTOR_KEYS):
+            for k in FACTOR_KEYS:   # likewise the flags of the factor penalty
+                del cfg[k]
         with open(os.path.join(args.log_dir, "config.json"), "w") as fp:
             json.dump(cfg, fp, indent=4)
     vsc = ConvolutionalMulVAE(args.dataset, args.samples_length, 80, args.latent_size, args.lr, args.alpha,
@@ -441,6 +458,18 @@ def main(argv=None):
             vsc.set_kl_schedule(kl_kind, **kl_kw)
         except ValueError as e:
             raise SystemExit(f"--kl-schedule / --free-bits: {e}")
+    if args.tc_weight is None and args.shared_weight is None and args.factor_warmup_steps != 0:
+        raise SystemExit("--factor-warmup-steps configures --tc-weight / --shared-weight: give one of them too (a resume "
+                         "without any of the three restores the saved configuration)")
+    if args.tc_weight is not None or args.shared_weight is not None:
+        if not args.train:
+            raise SystemExit("--tc-weight / --shared-weight: the factor penalty belongs to training (--train true)")
+        try:
+            vsc.set_factor_penalty(args.tc_weight if args.tc_weight is not None else 0.0,
+                                   args.shared_weight if args.shared_weight is not None else 0.0,
+                                   warmup_steps=args.factor_warmup_steps)
+        except ValueError as e:
+            raise SystemExit(f"--tc-weight / --shared-weight: {e}")
     dp = world > 1 or os.environ.get("DVAE_FORCE_DDP", "0") == "1"
     if dp:
         setup_data_parallel(vsc, args.seed)

@@ -49,7 +49,8 @@ extern "C" {
  * existing argument list, structure or constant moved.  Likewise the scheduled loss (dvae_loss_fwd_sched,
  * dvae_loss_bwd_sched, dvae_loss_sched_t, DVAE_LOSS_MAX_D): additive, and the suites of the two earlier additions pin 319.
  * Likewise the latent map's four entry points (dvae_tsne_nn, dvae_tsne_affinities, dvae_tsne_forces, dvae_tsne_update) and
- * the speaker adversary's two (dvae_adv_rows, dvae_adv_params). */
+ * the speaker adversary's two (dvae_adv_rows, dvae_adv_params), and the factor penalty's three (dvae_factor_ws_bytes,
+ * dvae_factor_fwd, dvae_factor_bwd). */
 #define DVAE_ABI_VERSION 319
 int dvae_version(void);
 
@@ -962,6 +963,44 @@ int dvae_adv_rows(const float* x, int64_t ldx, const int* labels, const float* w
 int dvae_adv_params(const float* x, int64_t ldx, const int* labels, const float* h, const float* g2, const float* g1,
                     const float* row_loss, const int* row_pred, float inv_rows, int R, int D, int H, int S, float* dw1,
                     int ldw1, float* db1, float* dw2, float* db2, float* out, void* stream);
+
+/* ---- total-correlation and shared-information penalty of the train step (ops.FactorPenaltyFn) ----
+ * The reference's loss_functionGVAE2 (disentangled_vae.py:310-327) is L1 plus KL and has no term on the two figures the latent
+ * report prints beside them; this ADDS the beta-TCVAE penalty of Chen et al. (2018) on the minibatch, forward and backward.
+ * Added at 319 without a new revision: purely additive.
+ * z, mu, lv [N, D] fp32, dense (the N = 2 Bh rows of a step, z an argument of its own); the S style columns first, the
+ * D - S content columns behind.  With a_jd = -(ln(2 pi) / 2 + lv_jd / 2), h_jd = expf(-lv_jd) / 2 and
+ *     t_ijd = a_jd - h_jd (z_id - mu_jd)^2          (dz = z - mu, q = dz dz, t = fma(-h, q, a): dvae_latent_lse's)
+ *     style_ij, content_ij = the sums of t_ijd over d < S, d >= S   (the 64 lanes of a wave by the xor tree 32 .. 1)
+ *     joint_ij = style_ij + content_ij
+ * dvae_factor_fwd (two launches) writes L [N, D + 3]: per row i the log-sum-exp over j of t_i.d (d = 0 .. D - 1), style,
+ *   content and joint, the maximum taken off before every exponential (expf, logf): a row far from every column keeps a
+ *   finite L.  A per-dimension sum runs over the columns j = w, w + 4, ... in order for w = 0 .. 3 and adds the four in that
+ *   order; a block's over j = l, l + 64, ... for l = 0 .. 63 and adds the 64 by the xor tree.  ws (dvae_factor_ws_bytes(N)
+ *   bytes, 4-byte aligned) receives own_i = joint_ii.  stats [5] = {tc_style, tc_content, shared, mi, penalty}, means over the
+ *   rows added in float64 in a fixed order (thread r of 256 the rows r, r + 256, ..., then a binary tree):
+ *     tc_style = mean_i[(L_style - ln N) - sum_{d < S} (L_d - ln N)]      tc_content likewise over d >= S
+ *     shared   = mean_i[L_joint - L_style - L_content + ln N]             mi = mean_i[own_i - (L_joint - ln N)]
+ *     penalty  = weights[0] (tc_style + tc_content) + weights[1] shared
+ *   weights: DEVICE pointer to {w_tc, w_sh}, the warm-up factor already applied.  penalty (may be null): one more float
+ *   that receives stats[4], for a caller that keeps `stats` and hands the penalty on as a tensor of its own.
+ * dvae_factor_bwd (one launch of 2 N workgroups: N own a row i and write dz [N, D], N own a column j and write dmu, dlv
+ *   [N, D]) reads L as dvae_factor_fwd left it and recomputes t; nothing of size N x N is stored.  With
+ *   p_A(j|i) = expf(A_ij - L_A(i)), c_joint = w_sh, c_style = c_content = w_tc - w_sh, c_d = -w_tc, each times gscale[0]
+ *   (DEVICE pointer to the incoming gradient of the penalty; null: 1), and r = 2 h_jd (z_id - mu_jd):
+ *     g_ijd = ((c_joint p_joint + c_block p_block(d)) + c_d p_d) / N
+ *     dz[i, d] = sum_j -g r     dmu[j, d] = sum_i g r     dlv[j, d] = sum_i g (r (z_id - mu_jd) / 2 - 1 / 2)
+ *   each sum in index order from +0, one fma per term.  When the device values of both weights are exactly 0, all three are
+ *   +0.0 everywhere whatever the inputs hold: a NaN in the statistics does not reach the model while the feature only monitors.
+ * No atomics; every order is a function of (N, D, S) alone: a row's L does not depend on which rows are in the launch beyond
+ * the columns they are, and two launches give the same bits.  Null pointers (penalty and gscale aside), N outside 1 .. DVAE_FACTOR_MAX_N,
+ * S < 1, D - S < 1 or D > DVAE_LATENT_MAX_D return DVAE_EINVAL and launch nothing (dvae_factor_ws_bytes: -1). */
+#define DVAE_FACTOR_MAX_N 1024
+int64_t dvae_factor_ws_bytes(int N);
+int dvae_factor_fwd(const float* z, const float* mu, const float* lv, int N, int D, int S, const float* weights, float* L,
+                    float* stats, float* penalty, void* ws, void* stream);
+int dvae_factor_bwd(const float* z, const float* mu, const float* lv, const float* L, int N, int D, int S,
+                    const float* weights, const float* gscale, float* dz, float* dmu, float* dlv, void* stream);
 
 /* ---- held-out validation (model/variational_base_vae.py: validate) ----
  * The reference's test() (variational_base_vae.py:105-123) sums loss_functionGVAE2 (disentangled_vae.py:310-327) over the
