@@ -3,7 +3,10 @@ data-parallel step — ops.grad_ready_hook -> GradReducer (bucketed all-reduce i
 HIP backward kernels are still being enqueued) -> FlatAdam(grad_scale) — runs on the HIP kernels.  Started as a FRESH
 process: nothing has touched the GPU before init_process_group.  Prints one JSON line.
 
-argv: <graph 0|1> <lr> <steps>"""
+argv: <graph 0|1> <lr> <steps> [features]
+features: both trainers run with the KL schedule and free bits, the factor penalty with its warm-up, gradient clipping at half the
+first step's norm (measured by a throwaway trainer) and the weight average on — no adversary, which is refused under a reducer —
+and the line gains `same` (torch.equal of the two trainers' state, name by name), the two host counters and the clip counters."""
 import json
 import os
 import sys
@@ -14,6 +17,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     use_graph, lr, steps = int(sys.argv[1]), float(sys.argv[2]), int(sys.argv[3])
+    features = len(sys.argv) > 4 and sys.argv[4] == "features"
     import torch
     import torch.distributed as dist
     torch.cuda.set_device(0)
@@ -25,11 +29,16 @@ def main():
 
     B, T = 4, 64
 
-    def make(with_reducer):
+    def make(with_reducer, max_norm=None):
         w = dvae_amd.ConvolutionalMulVAE("VCTK", T, 80, 32, lr, 0.01, 500, False, batch_size=B, speaker_size=4,
                                          device=dev, latent_dim=32, mse_cof=10, kl_cof=10)
         w.model.load_state_dict(fill_state_dict(w.model.state_dict()))
         w.model.train()
+        if max_norm is not None:
+            w.set_kl_schedule("linear", start=1.0, steps=6, free_bits=0.05)
+            w.set_factor_penalty(3.0, 1.5, warmup_steps=7)
+            w.optimizer.set_grad_clip(max_norm)
+            w.optimizer.set_ema(0.9)
         red = None
         if with_reducer:
             ddp.broadcast_parameters(w.optimizer.flat_p, list(w.model.buffers()))
@@ -42,8 +51,16 @@ def main():
                 w.enable_graph(True, ddp=True)
         return w, red
 
-    a, _ = make(False)
-    b, red = make(True)
+    max_norm = None
+    if features:
+        probe, _ = make(False)
+        probe.optimizer.set_grad_clip(float("inf"))
+        probe.model.eps_override = synthetic_eps(B, seed=200)
+        probe.step(*(t.cuda() for t in synthetic_pair(B, T, 100)), None, train=True)
+        max_norm = probe.optimizer.grad_clip_stats()["norm"] / 2
+        del probe
+    a, _ = make(False, max_norm)
+    b, red = make(True, max_norm)
     out = {"graph": use_graph, "lr": lr, "buckets": len(red.buckets), "losses_plain": [], "losses_ddp": []}
     for i in range(steps):
         x1, x2 = (t.cuda() for t in synthetic_pair(B, T, 100 + i))
@@ -67,6 +84,15 @@ def main():
     out["param_moved_rel"] = float(lr * steps * (a.optimizer.numel ** 0.5) / a.optimizer.flat_p.double().norm())
     ma, mb = a.optimizer.exp_avg, b.optimizer.exp_avg
     out["exp_avg_rel"] = float((ma - mb).norm() / ma.norm())
+    if features:
+        pairs = [(n, getattr(a.optimizer, n), getattr(b.optimizer, n)) for n in ("flat_p", "exp_avg", "exp_avg_sq", "ema", "clip_state")]
+        pairs += [("kl_aux", a.kl_aux, b.kl_aux), ("factor_aux", a.factor_aux, b.factor_aux)]
+        pairs += [("buffer " + n, u, v) for (n, u), (_, v) in zip(a.model.named_buffers(), b.model.named_buffers())]
+        out["same"] = {n: bool(torch.equal(u, v)) for n, u, v in pairs}
+        out["max_norm"] = max_norm
+        out["fac_k"], out["kl_k"] = [a._fac_k, b._fac_k], [a._kl_k, b._kl_k]
+        out["clipped"] = [a.optimizer.grad_clip_stats()["clipped"], b.optimizer.grad_clip_stats()["clipped"]]
+        out["skipped"] = [a.optimizer.grad_clip_stats()["skipped"], b.optimizer.grad_clip_stats()["skipped"]]
     print("DDPCHILD " + json.dumps(out), flush=True)
     dist.destroy_process_group()
 

@@ -3,7 +3,8 @@ child process (tests/_ddp_gpu_child.py) runs the same seeded steps through a pla
 ddp.GradReducer attached (`force`: collectives are issued although world_size == 1), eagerly and with the whole step —
 RCCL collectives included — captured into a hipGraph.  Checks: same losses / parameters / Adam moments as the
 non-data-parallel path, every bucket launched from the autograd hook (none left for finish(): the overlap contract),
-flat views intact.  Multi-rank arithmetic (sum over ranks, 1/world) is covered on CPU by tests/test_ddp_gloo.py."""
+flat views intact; and once with the KL schedule, free bits, the factor penalty, clipping and the weight average on in both
+trainers, bit for bit.  Multi-rank arithmetic (sum over ranks, 1/world) is covered on CPU by tests/test_ddp_gloo.py."""
 import json
 import os
 import socket
@@ -24,11 +25,13 @@ def _free_port():
     return p
 
 
-def _child(graph, lr, steps):
+def _child(graph, lr, steps, extra=(), timeout=600, env_drop=()):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_ddp_gpu_child.py"), str(graph), str(lr), str(steps)],
-                       env=env, capture_output=True, text=True, timeout=600)
+    for k in env_drop:
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_ddp_gpu_child.py"), str(graph), str(lr), str(steps),
+                        *extra], env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("DDPCHILD ")][-1]
     return json.loads(line[len("DDPCHILD "):])
@@ -64,6 +67,22 @@ def test_ddp_step_trains_like_plain_step(graph):
     # only (see _ddp_gpu_child.py): well under the distance either has travelled
     assert o["param_dist_rel"] <= 0.5 * o["param_moved_rel"], (o["param_dist_rel"], o["param_moved_rel"])
     assert o["views_intact"] and o["stats"]["finish"] == 0
+
+
+def test_ddp_step_with_the_features_on_equals_the_plain_step_bitwise():
+    """The KL schedule with free bits, the factor penalty (a second autograd root in the backward the hooks fire from), gradient
+    clipping at half the first step's norm and the weight average, on in both trainers: "all_reduce" mode, eager (with a
+    reducer attached the product runs eagerly unless DVAE_DDP_GRAPH=1), the default arithmetic, five steps at lr = 1e-4.  The
+    step is bit-deterministic since round 6, so everything is compared exactly."""
+    o = _child(0, 1e-4, 5, extra=("features",), timeout=900, env_drop=("DVAE_DETERMINISTIC", "DVAE_DDP_MODE", "DVAE_DDP_ISSUE"))
+    assert o["deterministic"] is False and o["ddp_mode"] == "all_reduce" and o["graph_captured"] is False
+    assert o["losses_plain"] == o["losses_ddp"], (o["losses_plain"], o["losses_ddp"])
+    assert {"flat_p", "exp_avg", "exp_avg_sq", "ema", "clip_state", "kl_aux", "factor_aux"} <= set(o["same"])
+    assert any(n.startswith("buffer ") for n in o["same"])
+    assert all(o["same"].values()), [n for n, v in o["same"].items() if not v]
+    assert o["stats"]["finish"] == 0 and o["stats"]["hook"] == 5 * o["buckets"], o["stats"]
+    assert min(o["clipped"]) >= 1 and o["skipped"] == [0, 0], (o["clipped"], o["skipped"], o["max_norm"])
+    assert o["t"] == [5, 5] and o["fac_k"] == [5, 5] and o["kl_k"] == [5, 5] and o["views_intact"]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
