@@ -556,16 +556,16 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
             raise RuntimeError("set_kl_schedule: the scheduled loss runs only on the HIP device (no CPU fallback)")
         if D > _lib.LOSS_MAX_D:
             raise ValueError(f"set_kl_schedule: {D} latent dimensions, the loss kernels take {_lib.LOSS_MAX_D}")
-        if getattr(self, "_kl_coef", None) is None:     # allocated once: a captured graph holds their addresses
+        if self._kl_coef is None:       # allocated once: a captured graph holds their addresses
             self._kl_coef = torch.zeros(8, device=dev, dtype=torch.float32)
             self.kl_aux = torch.zeros(4 + 4 * D, device=dev, dtype=torch.float32)
             self._kl_fb = torch.zeros(D, device=dev, dtype=torch.float32)
-            self._kl_pin, self._kl_pin_ev, self._kl_pin_i = None, None, 0
         if sched.free_bits is not None:
             self._kl_fb.copy_(torch.tensor(sched.free_bits, dtype=torch.float32))
         self.kl_sched = sched
         opt.kl_schedule = sched.params()        # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
-        self._kl_sent, self._kl_k, self.kl_weight = None, None, None
+        self._feature_set("kl")
+        self.kl_weight = None
 
     def set_speaker_adversary(self, weight=None, *, n_speakers=None, hidden=256, lr=1e-3, warmup_steps=0, seed=0):
         """A speaker classifier on the content means of every TRAINING step, trained inside the replayed graph, whose
@@ -595,17 +595,15 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         Cn = self.model.latent_dim - self.model.speaker_size
         cfg = dict(weight=weight, n_speakers=int(n_speakers), hidden=int(hidden), lr=float(lr), warmup_steps=warmup_steps,
                    seed=int(seed))
-        old = getattr(self, "adv_config", None)
-        same_net = getattr(self, "adversary", None) is not None and \
-            all(old[k] == cfg[k] for k in ("n_speakers", "hidden", "lr", "seed"))
+        same_net = self.adversary is not None and \
+            all(self.adv_config[k] == cfg[k] for k in ("n_speakers", "hidden", "lr", "seed"))
         if not same_net:        # a new classifier; only the weight or its warm-up changed: the one that is learning stays
             self.adversary = SpeakerAdversary(Cn, n_speakers, hidden=hidden, seed=seed, device=dev, lr=lr)
-        if getattr(self, "_adv_coef", None) is None:        # allocated once: a captured graph holds its address
+        if self._adv_coef is None:      # allocated once: a captured graph holds its address
             self._adv_coef = torch.zeros(1, device=dev, dtype=torch.float32)
-            self._adv_pin, self._adv_pin_ev, self._adv_pin_i = None, None, 0
         self.adv_config = cfg
-        self._adv_sent, self._adv_k, self.adv_weight = None, None, None
-        self.adv_out = self.adv_pred = self.adv_stats = None
+        self._feature_set("adv")
+        self.adv_weight = self.adv_out = self.adv_pred = self.adv_stats = None
 
     def set_factor_penalty(self, tc_weight=None, shared_weight=0.0, *, warmup_steps=0):
         """The beta-TCVAE penalty (Chen et al. 2018) on the minibatch of every TRAINING step, inside the replayed graph
@@ -643,19 +641,18 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         dev = opt.flat_p.device
         if dev.type != "cuda":
             raise RuntimeError("set_factor_penalty: the penalty runs only on the HIP device (no CPU fallback)")
-        if getattr(self, "_fac_coef", None) is None:        # allocated once: a captured graph holds their addresses
+        if self._fac_coef is None:      # allocated once: a captured graph holds their addresses
             self._fac_coef = torch.zeros(2, device=dev, dtype=torch.float32)
             self.factor_aux = torch.zeros(5, device=dev, dtype=torch.float32)
-            self._fac_pin, self._fac_pin_ev, self._fac_pin_i = None, None, 0
         self.factor_cfg = dict(tc_weight=tc_weight, shared_weight=shared_weight, warmup_steps=warmup_steps)
         self.model.factor_tap = True
         opt.factor_penalty = dict(self.factor_cfg)      # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
-        self._fac_sent, self._fac_k, self.factor_weights = None, None, None
-        self.factor_stats = None
+        self._feature_set("factor")
+        self.factor_weights = self.factor_stats = None
 
     def kl_weight_at(self, k, epoch=1):
         """The KL weight of the step that runs after `k` optimiser steps, in epoch `epoch` (kl_schedule.KLSchedule)."""
-        if getattr(self, "kl_sched", None) is None:
+        if self.kl_sched is None:
             return float(self.kl_cof)
         return self.kl_sched.weight_at(k, epoch, self.kl_cof)
 
@@ -663,7 +660,7 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         """losses_vector on the unsplit outputs of `DisentangledVAE.forward_full` (the training step's path).  While a KL
         schedule is on (set_kl_schedule) the weights come from the device and `self.kl_aux` receives the per-dimension KL."""
         inv_b = 1.0 / float(self.batch_size)
-        sched = getattr(self, "kl_sched", None)
+        sched = self.kl_sched
         if sched is not None:
             return ops.LossGVAE2SchedFn.apply(x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv, inv_b, -0.5 / x1.shape[0], -inv_b,
                                               self._kl_coef, self._kl_fb if sched.free_bits is not None else None,

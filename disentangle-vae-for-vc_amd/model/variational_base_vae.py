@@ -22,6 +22,19 @@ from pathlib import Path
 
 import torch
 
+from ..optim import ScalarSender
+
+
+def named_to_host(parts):
+    """{name: 1-D device tensor} -> {name: list of floats}: every tensor as float64, ONE concatenation, ONE device-to-host copy,
+    cut back by name."""
+    flat = torch.cat([t.double() for t in parts.values()]).tolist()
+    out, o = {}, 0
+    for name, t in parts.items():
+        out[name] = flat[o:o + t.numel()]
+        o += t.numel()
+    return out
+
 
 def chunking_mel(melspectrogram, n_frames: int = 64, device="cuda"):
     """[80, L] (numpy or tensor) -> device tensor [L//T + 1, 80, T], tail zero-padded — the reference's chunking_mel
@@ -57,13 +70,26 @@ class VariationalBaseModelVAE:
         self._graph = None
         self._graph_sig = None
         self._graph_calls = 0
+        # the opt-in features of the train step (the subclass's set_kl_schedule / set_speaker_adversary / set_factor_penalty):
+        # None is "off".  Their weights at optimiser step k are device scalars, sent before the step by _sync_step_coefs
+        self.kl_sched = self.adversary = self.adv_config = self.factor_cfg = None
+        self.kl_weight = self.adv_weight = self.factor_weights = None      # as last computed for a step (float, float, pair)
+        self.kl_stats = self.kl_dims = self.adv_stats = self.factor_stats = self.grad_stats = self.ema_stats = None
+        self.adv_out = self.adv_pred = None
+        self._step_k = None         # the host's count of optimizer.t (None: read it before the next step)
+        self._kl_epoch = 1
+        self._kl_coef = self._adv_coef = self._fac_coef = None      # the device scalars: allocated once, by the setters
+        self._coef_sent = {}        # feature -> the weights its device scalars hold
+        self._sender = ScalarSender()
+        self._loss_seed = None
+        self._fold_before_shard = None
 
     def loss_function(self):
         raise NotImplementedError
 
     # ---- data parallel (new functionality: the reference is single-device)
     def attach_reducer(self, reducer):
-        if reducer is not None and getattr(self, "adversary", None) is not None:
+        if reducer is not None and self.adversary is not None:
             raise ValueError("attach_reducer: the speaker adversary (set_speaker_adversary) is not trained data parallel: its "
                              "gradients are not reduced; switch it off first")
         sharded = reducer is not None and getattr(reducer, "mode", "all_reduce") == "rs_ag"
@@ -78,12 +104,12 @@ class VariationalBaseModelVAE:
             # next reducer that is not sharded (or with None), so switching modes back and forth leaves no trace
             opt = self.optimizer
             if sharded:
-                if getattr(self, "_fold_before_shard", None) is None:
+                if self._fold_before_shard is None:
                     self._fold_before_shard = bool(opt.fold_zero_grad)
                 if opt.fold_zero_grad:
                     opt.fold_zero_grad = False
                     opt._clean = False
-            elif getattr(self, "_fold_before_shard", None) is not None:
+            elif self._fold_before_shard is not None:
                 if opt.fold_zero_grad != self._fold_before_shard:
                     opt.fold_zero_grad = self._fold_before_shard
                     opt._clean = False
@@ -123,14 +149,14 @@ class VariationalBaseModelVAE:
 
     def _adv_signature(self):
         """The speaker adversary on/off and its shape change the launches of a step; its weight does not (a device scalar,
-        _sync_adv_coef).  Nothing is added while it is off."""
-        adv = getattr(self, "adversary", None)
+        _sync_step_coefs).  Nothing is added while it is off."""
+        adv = self.adversary
         return (("adv", adv.hidden, adv.n_speakers),) if adv is not None else ()
 
     def _factor_signature(self):
         """The factor penalty on/off changes the launches of a step; its two weights and their warm-up do not (device scalars,
-        _sync_factor_coef).  Nothing is added while it is off."""
-        return (("factor",),) if getattr(self, "factor_cfg", None) is not None else ()
+        _sync_step_coefs).  Nothing is added while it is off."""
+        return (("factor",),) if self.factor_cfg is not None else ()
 
     def factor_weights_at(self, k):
         """(w_tc, w_sh) of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
@@ -139,61 +165,55 @@ class VariationalBaseModelVAE:
         f = 1.0 if n <= 0 else min(1.0, k / n)
         return float(cfg["tc_weight"]) * f, float(cfg["shared_weight"]) * f
 
-    def _sync_factor_coef(self):
-        """Host -> device copy of the penalty's two weights for the step about to run when they changed since the last copy;
-        beside _sync_kl_coef and _sync_adv_coef, never inside a capture.  The step's number is the optimiser's step count,
-        kept by the host as `_fac_k` exactly as `_kl_k` is."""
-        if getattr(self, "factor_cfg", None) is None:
-            return
-        if self._fac_k is None:
-            self._fac_k = self.optimizer.t
-        pair = self.factor_weights_at(self._fac_k)
-        if pair != self._fac_sent:
-            if self._fac_pin is None:
-                self._fac_pin = torch.empty(16, 2, dtype=torch.float32, pin_memory=True)
-                self._fac_pin_ev = [None] * 16
-            i = self._fac_pin_i = (self._fac_pin_i + 1) % 16
-            if self._fac_pin_ev[i] is not None:
-                self._fac_pin_ev[i].synchronize()
-            self._fac_pin[i, 0], self._fac_pin[i, 1] = pair
-            self._fac_coef[0:2].copy_(self._fac_pin[i], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._fac_pin_ev[i] = ev
-            self._fac_sent = pair
-        self.factor_weights = pair
-        self._fac_k += 1
-
     def adv_weight_at(self, k):
         """The reversal weight of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
         cfg = self.adv_config
         w, n = float(cfg["weight"]), int(cfg["warmup_steps"])
         return w if n <= 0 else w * min(1.0, k / n)
 
-    def _sync_adv_coef(self):
-        """Host -> device copy of the reversal weight of the step about to run when it changed since the last copy; beside
-        _sync_kl_coef, never inside a capture.  The step's number is the model optimiser's step count, kept by the host as
-        `_adv_k` exactly as `_kl_k` is."""
-        if getattr(self, "adversary", None) is None:
-            return
-        if self._adv_k is None:
-            self._adv_k = self.optimizer.t
-        w = float(self.adv_weight_at(self._adv_k))
-        if w != self._adv_sent:
-            if self._adv_pin is None:
-                self._adv_pin = torch.empty(16, 1, dtype=torch.float32, pin_memory=True)
-                self._adv_pin_ev = [None] * 16
-            i = self._adv_pin_i = (self._adv_pin_i + 1) % 16
-            if self._adv_pin_ev[i] is not None:
-                self._adv_pin_ev[i].synchronize()
-            self._adv_pin[i, 0] = w
-            self._adv_coef[0:1].copy_(self._adv_pin[i], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._adv_pin_ev[i] = ev
-            self._adv_sent = w
-        self.adv_weight = w
-        self._adv_k += 1
+    def _feature_set(self, feature):
+        """A setter switched `feature` ("kl", "adv", "factor") on or reconfigured it: its device scalars are sent afresh, and
+        every feature takes the optimiser's true step count at the next step (one read of FlatAdam.t)."""
+        self._coef_sent.pop(feature, None)
+        self._step_k = None
+
+    def _sync_step_coefs(self):
+        """Host -> device copy of the weights of the step about to run, for every feature that is on and whose weights changed
+        since its last copy: (mse_cof, KL weight) of a schedule, the adversary's reversal weight, the penalty's pair.  Beside
+        optimizer.sync_scalars, never inside a capture.  The step about to run is number `_step_k` by the host's ONE count,
+        which starts from FlatAdam.t (one read) and is set right from it wherever the host reads the device anyway."""
+        if self.kl_sched is None and self.adversary is None and self.factor_cfg is None:
+            return              # the plain trainer: no read of optimizer.t (a device-to-host sync), no count
+        if self._step_k is None:
+            self._step_k = self.optimizer.t
+        k, want = self._step_k, {}
+        if self.kl_sched is not None:
+            self.kl_weight = float(self.kl_weight_at(k, self._kl_epoch))
+            want["kl"] = (self._kl_coef, (float(self.mse_cof), self.kl_weight))
+        if self.adversary is not None:
+            self.adv_weight = float(self.adv_weight_at(k))
+            want["adv"] = (self._adv_coef, (self.adv_weight,))
+        if self.factor_cfg is not None:
+            self.factor_weights = self.factor_weights_at(k)
+            want["factor"] = (self._fac_coef, self.factor_weights)
+        send = {f: bv for f, bv in want.items() if self._coef_sent.get(f) != bv[1]}
+        if send:
+            # through the ring of pinned slots (optim.ScalarSender): a per-step schedule must not stall the host
+            self._sender.send([(buf[:len(vals)], vals) for buf, vals in send.values()])
+            self._coef_sent.update((f, vals) for f, (_, vals) in send.items())
+        self._step_k += 1       # Adam advances t with this step (or skips it: set right at the next read of t)
+
+    def _prepare_step(self, dev):
+        """Everything of the host's that has to happen before a step and never inside a capture, in one place: _step_graph
+        calls it before capture / replay, the eager step when _step_graph has not."""
+        adv = self.adversary
+        if adv is not None:
+            self._sync_adv_guard()              # may allocate the buffers of the adversary's non-finite guard
+            adv.optimizer.sync_scalars(1.0)     # after the first step nothing: its step() sends the same value
+        if adv is not None or self.factor_cfg is not None:
+            from .. import ops
+            ops.unit_seed(dev)                  # allocated outside the capture
+        self._sync_step_coefs()
 
     def _adv_labels(self, speaker_ids, out=None):
         """speaker_ids [Bh] (host or device, any integer type) -> the [2 Bh] int32 device labels of the rows of q_mu (the x1
@@ -211,36 +231,9 @@ class VariationalBaseModelVAE:
 
     def _kl_signature(self):
         """A KL schedule on/off, and free bits on/off, change the loss launches of a step; the weight does not (a device
-        scalar, _sync_kl_coef).  Nothing is added while it is off."""
-        sched = getattr(self, "kl_sched", None)
+        scalar, _sync_step_coefs).  Nothing is added while it is off."""
+        sched = self.kl_sched
         return (("kl_sched", sched.free_bits is not None),) if sched is not None else ()
-
-    def _sync_kl_coef(self):
-        """Host -> device copy of (mse_cof, the KL weight of the step about to run) when the pair changed since the last
-        copy; beside optimizer.sync_scalars, never inside a capture.  The step about to run is number `_kl_k` by the host's
-        count, which starts from FlatAdam.t (one read) and is set right from it wherever the host reads the device anyway."""
-        if getattr(self, "kl_sched", None) is None:
-            return
-        if self._kl_k is None:
-            self._kl_k = self.optimizer.t
-        w = self.kl_weight_at(self._kl_k, getattr(self, "_kl_epoch", 1))
-        pair = (float(self.mse_cof), float(w))
-        if pair != self._kl_sent:
-            # staged through a small ring of pinned slots like FlatAdam.sync_scalars: a per-step schedule must not stall the host
-            if self._kl_pin is None:
-                self._kl_pin = torch.empty(16, 2, dtype=torch.float32, pin_memory=True)
-                self._kl_pin_ev = [None] * 16
-            i = self._kl_pin_i = (self._kl_pin_i + 1) % 16
-            if self._kl_pin_ev[i] is not None:
-                self._kl_pin_ev[i].synchronize()
-            self._kl_pin[i, 0], self._kl_pin[i, 1] = pair
-            self._kl_coef[0:2].copy_(self._kl_pin[i], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            self._kl_pin_ev[i] = ev
-            self._kl_sent = pair
-        self.kl_weight = float(w)
-        self._kl_k += 1         # Adam advances t with this step (or skips it: set right at the next read of t)
 
     def _clip_signature(self):
         """Gradient clipping on/off and the guard change the launches of a step; the VALUE of max_norm does not (a device
@@ -261,14 +254,11 @@ class VariationalBaseModelVAE:
         averages already, and are the same inside and outside."""
         return self.optimizer.ema_weights()
 
-    def _eager_train_step(self, data1, data2, kl_sent=False, labels2=None):
+    def _eager_train_step(self, data1, data2, prepared=False, labels2=None):
         # (until round 5 the step ran inside an ops.ZeroArena: one clear launch for the outputs that split-k contractions
         # accumulated into atomically; split contractions store slabs now and nothing needs clearing)
-        if not kl_sent:                 # _step_graph sends the weights of a KL schedule itself, before capture / replay
-            self._sync_kl_coef()
-            self._sync_adv_guard()
-            self._sync_adv_coef()       # likewise the adversary's reversal weight
-            self._sync_factor_coef()    # ... and the factor penalty's two weights
+        if not prepared:                # _step_graph has prepared the step itself, before capture / replay
+            self._prepare_step(data1.device)
         return self._train_step_body(data1, data2, labels2)
 
     def _sync_adv_guard(self):
@@ -276,29 +266,27 @@ class VariationalBaseModelVAE:
         feed NaNs into the other's moments.  The first set_grad_clip allocates: like every other host-side refresh this runs
         before the step, never inside a capture (the model's guard is part of the graph signature, so switching it captures
         again, after this)."""
-        adv = getattr(self, "adversary", None)
-        if adv is None:
-            return
+        adv = self.adversary
         guard = getattr(self.optimizer, "max_norm", None) is not None
         if guard != (adv.optimizer.max_norm is not None):
             adv.optimizer.set_grad_clip(float("inf") if guard else None, skip_nonfinite=True)
 
     def _train_step_body(self, data1, data2, labels2=None):
         self.optimizer.zero_grad()
-        adv = getattr(self, "adversary", None)
+        adv, fac = self.adversary, self.factor_cfg
+        unsplit = hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full")
         outs = None
         if adv is not None:
             if labels2 is None:
                 raise ValueError("the speaker adversary is on (set_speaker_adversary): the step needs speaker_ids")
-            if not (hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full")):
+            if not unsplit:
                 raise RuntimeError("the speaker adversary needs the unsplit forward (forward_full / losses_vector_full)")
             if self.reducer is not None:
                 raise ValueError("the speaker adversary is not trained data parallel")
             adv.optimizer.zero_grad()       # store-first parameters only: no launch, the written-once counts start over
-        fac = getattr(self, "factor_cfg", None)
-        if fac is not None and not (hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full")):
+        if fac is not None and not unsplit:
             raise RuntimeError("the factor penalty needs the unsplit forward (forward_full / losses_vector_full)")
-        if hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full"):
+        if unsplit:
             # the eight scalars as one vector (fused loss kernels) on the UNSPLIT outputs; backward is seeded with the
             # constant (1, 0, ..., 0): `vec[0].backward()` and the reference's ten output slices cost ~25 zero-fill /
             # copy launches of autograd glue per step
@@ -311,7 +299,7 @@ class VariationalBaseModelVAE:
         if self.reducer is not None:
             self.reducer.begin()
         if vec is not None:
-            if getattr(self, "_loss_seed", None) is None or self._loss_seed.device != vec.device:
+            if self._loss_seed is None or self._loss_seed.device != vec.device:
                 self._loss_seed = torch.zeros(8, device=vec.device)
                 self._loss_seed[0] = 1.0
             roots, seeds = [vec], [self._loss_seed]
@@ -355,7 +343,7 @@ class VariationalBaseModelVAE:
         Bh = data1.shape[0]
         S, Cn = m.speaker_size, m.latent_dim - m.speaker_size
         self._graph_calls += 1
-        adv = getattr(self, "adversary", None)
+        adv = self.adversary
         if self._graph_calls == 1:
             return self._eager_train_step(data1, data2, labels2=self._adv_labels(speaker_ids) if adv is not None else None)
         sig = self._graph_signature(data1)
@@ -383,17 +371,7 @@ class VariationalBaseModelVAE:
         m.eps_override = self._g_eps
         # learning rate / gradient scale: device scalars, refreshed OUTSIDE the captured region
         self.optimizer.sync_scalars(1.0 / self.reducer.world_size if self.reducer is not None else 1.0)
-        self._sync_kl_coef()            # likewise the loss weights of a KL schedule (nothing while it is off)
-        if adv is not None:
-            from .. import ops
-            ops.unit_seed(dev)          # allocated outside the capture
-            self._sync_adv_guard()      # ... as are the buffers of the adversary's non-finite guard
-            adv.optimizer.sync_scalars(1.0)
-            self._sync_adv_coef()       # ... and the adversary's reversal weight
-        if getattr(self, "factor_cfg", None) is not None:
-            from .. import ops
-            ops.unit_seed(dev)          # allocated outside the capture
-            self._sync_factor_coef()    # the factor penalty's two weights (nothing while it is off)
+        self._prepare_step(dev)         # likewise what the opt-in features need (nothing while they are off)
         if self._graph is not None and not getattr(self.optimizer, "_clean", True):
             # something accumulated into the gradient buffer since the last Adam launch (a manual backward between two
             # replays): a graph captured on a clean buffer holds no zero_grad launch of its own
@@ -421,7 +399,7 @@ class VariationalBaseModelVAE:
                     _time.sleep(0.5)
                 try:
                     with torch.cuda.graph(g, **mode):
-                        self._g_losses = self._eager_train_step(self._g_x1, self._g_x2, kl_sent=True, labels2=self._g_labels2)
+                        self._g_losses = self._eager_train_step(self._g_x1, self._g_x2, prepared=True, labels2=self._g_labels2)
                 except Exception as e:      # nothing of the step has run: fall back to the eager step, for good
                     if self.reducer is None:
                         raise
@@ -431,7 +409,7 @@ class VariationalBaseModelVAE:
                     self._use_graph = False
                     self._graph = None
                     torch.cuda.synchronize()
-                    return self._eager_train_step(self._g_x1, self._g_x2, kl_sent=True, labels2=self._g_labels2)
+                    return self._eager_train_step(self._g_x1, self._g_x2, prepared=True, labels2=self._g_labels2)
                 self._graph = g
             self._graph.replay()
             if getattr(self.optimizer, "fold_zero_grad", False):
@@ -446,21 +424,15 @@ class VariationalBaseModelVAE:
         train=True)` is this plus one device->host copy."""
         if self._use_graph and (self.reducer is None or self._graph_ddp):
             return self._step_graph(data1, data2, speaker_ids)
-        adv = getattr(self, "adversary", None)
+        adv = self.adversary
         return self._eager_train_step(data1, data2, labels2=self._adv_labels(speaker_ids) if adv is not None else None)
 
     # ---- variational_base_vae.py:58-70
     def step(self, data1, data2, speaker_ids, train=False):
-        if train and (getattr(self, "kl_sched", None) is not None or getattr(self, "adversary", None) is not None
-                      or getattr(self, "factor_cfg", None) is not None):
-            # the same one copy carries the optimiser's step count: the schedule's position is exactly t (a skipped step)
+        if train and (self.kl_sched is not None or self.adversary is not None or self.factor_cfg is not None):
+            # the same one copy carries the optimiser's step count: the schedules' position is exactly t (a skipped step)
             vec = torch.cat([self.step_async(data1, data2, speaker_ids), self.optimizer.dev_state[0:1]]).tolist()
-            if getattr(self, "kl_sched", None) is not None:
-                self._kl_k = int(vec[8])
-            if getattr(self, "adversary", None) is not None:
-                self._adv_k = int(vec[8])
-            if getattr(self, "factor_cfg", None) is not None:
-                self._fac_k = int(vec[8])
+            self._step_k = int(vec[8])
             self._check_and_recover()
             return tuple(vec[:8])
         if train:
@@ -493,106 +465,95 @@ class VariationalBaseModelVAE:
         self.model.train()
         # the running sums of :88-96 live on the device (fp64); the host reads them once per epoch instead of
         # stalling the queue after every step
-        tot = torch.zeros(8, dtype=torch.float64, device=self.device)
-        last = None
-        # gradient clipping on: the step's norm (optimizer.clip_state[1]) joins running sum / max tensors the same way; a
-        # norm that is not finite in float32 (a skipped step, or a huge gradient that was clipped) is counted, not averaged
+        f64 = lambda n: torch.zeros(n, dtype=torch.float64, device=self.device)
+        tot = f64(8)
+        last, steps = None, 0
         opt = self.optimizer
         clip = getattr(opt, "max_norm", None) is not None
-        self.grad_stats = None
         ema = getattr(opt, "ema_decay", None) is not None
-        self.ema_stats = None
+        sched, adv, fac = self.kl_sched, self.adversary, self.factor_cfg
+        self.grad_stats = self.ema_stats = self.kl_stats = self.kl_dims = self.adv_stats = self.factor_stats = None
+        # gradient clipping on: the step's norm (optimizer.clip_state[1]) joins running sum / max tensors the same way; a
+        # norm that is not finite in float32 (a skipped step, or a huge gradient that was clipped) is counted, not averaged
         if clip:
-            gsum = torch.zeros(2, dtype=torch.float64, device=self.device)      # sum of the finite norms, their number
+            gsum = f64(2)           # sum of the finite norms, their number
             gmax = torch.zeros(1, dtype=torch.float32, device=self.device)
             zero = torch.zeros(1, dtype=torch.float32, device=self.device)
             before = opt.clip_state[5:7].clone()
         # a KL schedule on (set_kl_schedule): the free counts and the per-dimension KL of every step (kl_aux[2 : 4 + 2 D]) join
-        # a running float64 tensor the same way, and the optimiser's step count rides along to set the schedule's position right
-        sched = getattr(self, "kl_sched", None)
-        self.kl_stats = self.kl_dims = None
+        # a running float64 tensor the same way
         if sched is not None:
             self._kl_epoch = max(1, int(epoch))
             kD = (self.kl_aux.numel() - 4) // 4
-            ksum = torch.zeros(2 + 2 * kD, dtype=torch.float64, device=self.device)
-            ksteps = 0
-        # the speaker adversary on (set_speaker_adversary): its four statistics of every step join a running float64 tensor
-        adv = getattr(self, "adversary", None)
-        self.adv_stats = None
+            ksum = f64(2 + 2 * kD)
+        # likewise the four statistics of the speaker adversary (set_speaker_adversary) and the five of the factor penalty
+        # (set_factor_penalty)
         if adv is not None:
-            asum = torch.zeros(4, dtype=torch.float64, device=self.device)
-        # the factor penalty on (set_factor_penalty): its five statistics of every step join a running float64 tensor
-        fac = getattr(self, "factor_cfg", None)
-        self.factor_stats = None
+            asum = f64(4)
         if fac is not None:
-            fsum = torch.zeros(5, dtype=torch.float64, device=self.device)
-            fsteps = 0
+            fsum = f64(5)
         for data1, data2, speaker_ids in train_loader:
             data1 = data1.to(self.device, non_blocking=True).float()
             data2 = data2.to(self.device, non_blocking=True).float()
             speaker_ids = speaker_ids.view(-1)
             last = self.step_async(data1, data2, speaker_ids)
+            steps += 1
             tot.add_(last)
             if adv is not None:
                 asum.add_(self.adv_out)
             if fac is not None:
                 fsum.add_(self.factor_aux)
-                fsteps += 1
             if sched is not None:
                 ksum.add_(self.kl_aux[2:4 + 2 * kD])
-                ksteps += 1
             if clip:
                 ok = torch.isfinite(opt.clip_state[1:2])
                 norm = torch.where(ok, opt.clip_state[1:2], zero)
                 gsum.add_(torch.cat([norm, ok.float()]))
                 torch.maximum(gmax, norm, out=gmax)
+        # the epoch's ONE device-to-host copy: every running tensor that is on, by name; while a feature with a schedule is on
+        # the optimiser's step count rides along and sets the host's count right
+        parts = {"loss": tot}
+        if sched is not None:
+            parts["kl"] = ksum
         if adv is not None:
-            # one more small copy per epoch: the sums, and the optimiser's step count to set the weight's position right
-            a = torch.cat([asum, opt.dev_state[0:1].double()]).tolist()
-            self._adv_k = int(a[4])
+            parts["adv"] = asum
+        if fac is not None:
+            parts["factor"] = fsum
+        if clip:
+            parts.update(gsum=gsum, gmax=gmax, clip_counts=opt.clip_state[5:7] - before)
+        if ema:
+            parts["ema"] = opt.ema_state[1:3]
+        if sched is not None or adv is not None or fac is not None:
+            parts["t"] = opt.dev_state[0:1]
+        host = named_to_host(parts)
+        tot, n = host["loss"], max(1, steps)
+        if "t" in host:
+            self._step_k = int(host["t"][0])
+        if adv is not None:
+            a = host["adv"]
             self.adv_stats = {"Adv/CE": a[0] / a[1] if a[1] else float("nan"),
                               "Adv/Accuracy": a[2] / a[1] if a[1] else float("nan"),
-                              "Adv/Weight": self.adv_weight if self.adv_weight is not None else self.adv_weight_at(self._adv_k)}
+                              "Adv/Weight": self.adv_weight if self.adv_weight is not None else self.adv_weight_at(self._step_k)}
         if fac is not None:
-            # likewise: the five sums, and the optimiser's step count to set the warm-up's position right
-            f = torch.cat([fsum, opt.dev_state[0:1].double()]).tolist()
-            self._fac_k = int(f[5])
-            n = max(1, fsteps)
-            w = self.factor_weights if self.factor_weights is not None else self.factor_weights_at(self._fac_k)
+            f = host["factor"]
+            w = self.factor_weights if self.factor_weights is not None else self.factor_weights_at(self._step_k)
             self.factor_stats = {"Factor/TC style": f[0] / n, "Factor/TC content": f[1] / n, "Factor/Shared": f[2] / n,
                                  "Factor/MI": f[3] / n, "Factor/Penalty": f[4] / n, "Factor/Weight tc": w[0],
                                  "Factor/Weight shared": w[1]}
-        ktail = []
         if sched is not None:
-            tot = torch.cat([tot, ksum, opt.dev_state[0:1].double()])     # behind the eight sums, in front of the rest
-        if clip:
-            # the epoch's single copy carries them along
-            packed = torch.cat([tot, gsum, gmax.double(), (opt.clip_state[5:7] - before).double()]
-                               + ([opt.ema_state[1:3].double()] if ema else [])).tolist()
-            if sched is not None:
-                ktail, packed = packed[8:11 + 2 * kD], packed[:8] + packed[11 + 2 * kD:]
-            tot = packed[:8]
-            self.grad_stats = {"Grad/Norm mean": packed[8] / max(1.0, packed[9]), "Grad/Norm max": packed[10],
-                               "Grad/Skipped steps": int(packed[11]), "Grad/Clipped steps": int(packed[12])}
-        elif ema:
-            packed = torch.cat([tot, opt.ema_state[1:3].double()]).tolist()
-            if sched is not None:
-                ktail = packed[8:11 + 2 * kD]
-            tot = packed[:8]
-        else:
-            tot = tot.tolist()
-            if sched is not None:
-                ktail, tot = tot[8:], tot[:8]
-        if sched is not None:
-            self._kl_k = int(ktail[-1])
-            n = max(1, ksteps)
-            z1, z2 = [v / n for v in ktail[2:2 + kD]], [v / n for v in ktail[2 + kD:2 + 2 * kD]]
-            self.kl_dims = {"epoch": epoch, "steps": ksteps, "z1": z1, "z2": z2}
-            self.kl_stats = {"KL/Weight": self.kl_weight if self.kl_weight is not None else self.kl_weight_at(self._kl_k, self._kl_epoch),
-                             "KL/Free dims z1": ktail[0] / n, "KL/Free dims z2": ktail[1] / n,
+            k = host["kl"]
+            z1, z2 = [v / n for v in k[2:2 + kD]], [v / n for v in k[2 + kD:2 + 2 * kD]]
+            self.kl_dims = {"epoch": epoch, "steps": steps, "z1": z1, "z2": z2}
+            self.kl_stats = {"KL/Weight": self.kl_weight if self.kl_weight is not None
+                             else self.kl_weight_at(self._step_k, self._kl_epoch),
+                             "KL/Free dims z1": k[0] / n, "KL/Free dims z2": k[1] / n,
                              "KL/Active dims": sum(1 for v in z1 if v > 0.01)}
+        if clip:
+            g = host["gsum"]
+            self.grad_stats = {"Grad/Norm mean": g[0] / max(1.0, g[1]), "Grad/Norm max": host["gmax"][0],
+                               "Grad/Skipped steps": int(host["clip_counts"][0]), "Grad/Clipped steps": int(host["clip_counts"][1])}
         if ema:
-            self.ema_stats = {"EMA/Updates": int(packed[-2]), "EMA/Weight": packed[-1]}
+            self.ema_stats = {"EMA/Updates": int(host["ema"][0]), "EMA/Weight": host["ema"][1]}
         self._check_and_recover()
         last_style = float(last[7]) if last is not None else 0.0
         if hasattr(train_loader, "dataset") and hasattr(train_loader.dataset, "shuffle_data"):
@@ -716,43 +677,38 @@ class VariationalBaseModelVAE:
                                         "average (train with --ema-decay / FlatAdam.set_ema)")
         # the speaker adversary of the run (`<base>.adv.pth`): checked before anything is loaded
         adv_path, adv_sd = last[:-4] + ".adv.pth", None
-        if getattr(self, "adversary", None) is None and not restore_adversary:
+        if self.adversary is None and not restore_adversary:
             pass
         elif os.path.exists(adv_path):
             adv_sd = torch.load(adv_path, map_location="cpu")
-            want = getattr(self, "adv_config", None) if getattr(self, "adversary", None) is not None else None
+            want = self.adv_config if self.adversary is not None else None
             if want is not None and dict(want) != dict(adv_sd["config"]):
                 raise ValueError(f"{adv_path} was trained with the speaker adversary {dict(adv_sd['config'])}, this run asks "
                                  f"for {dict(want)}: resume with the same flags (or with none: the saved ones are restored), or "
                                  "start a new run")
-        elif getattr(self, "adversary", None) is not None:
+        elif self.adversary is not None:
             raise ValueError(f"{adv_path} is missing: the last checkpoint ({last}) was written without a speaker adversary, "
                              "and one cannot join a run half way (its classifier would start untrained against a trained "
                              "encoder); start a new run")
         self.model.load_state_dict(torch.load(weights, map_location=self.device))
         if adv_sd is not None and not use_ema and hasattr(self, "set_speaker_adversary"):
-            if getattr(self, "adversary", None) is None:
+            if self.adversary is None:
                 cfg = dict(adv_sd["config"])
                 self.set_speaker_adversary(cfg.pop("weight"), **cfg)
             self.adversary.load_state_dict(adv_sd["adversary"])
-            self._adv_k = None
         opt = last[:-4] + ".opt"
         if os.path.exists(opt):
             sd = torch.load(opt, map_location="cpu")
             self.optimizer.load_state_dict(sd, legacy_layout=os.environ.get("DVAE_OPT_LEGACY_LAYOUT"))
             # the KL schedule the checkpoint was trained under (load_state_dict has refused a different one): restored when
-            # none was asked for, and continued either way at the step count just loaded
+            # none was asked for, and continued either way at the step count just loaded (`_step_k` below)
             saved = sd.get("kl_schedule")
-            if saved is not None and getattr(self, "kl_sched", None) is None and hasattr(self, "set_kl_schedule"):
+            if saved is not None and self.kl_sched is None and hasattr(self, "set_kl_schedule"):
                 self.set_kl_schedule(saved["kind"], **{k: saved[k] for k in ("start", "steps", "cycles", "ratio", "free_bits")})
-            if getattr(self, "kl_sched", None) is not None:
-                self._kl_k = None
             # likewise the factor penalty (load_state_dict has refused a different one)
             saved = sd.get("factor_penalty")
-            if saved is not None and getattr(self, "factor_cfg", None) is None and hasattr(self, "set_factor_penalty"):
+            if saved is not None and self.factor_cfg is None and hasattr(self, "set_factor_penalty"):
                 self.set_factor_penalty(saved["tc_weight"], saved["shared_weight"], warmup_steps=saved["warmup_steps"])
-            if getattr(self, "factor_cfg", None) is not None:
-                self._fac_k = None
             if sd.get("cuda_rng_state") is not None and torch.device(self.device).type == "cuda":
                 g = torch.cuda.default_generators[torch.device(self.device).index or 0]
                 if self.reducer is not None and self.reducer.rank > 0:
@@ -765,6 +721,7 @@ class VariationalBaseModelVAE:
                         g.set_offset(int(sd["cuda_rng_offset"]))
                 else:
                     torch.cuda.set_rng_state(sd["cuda_rng_state"], self.device)   # eps stream continues where it stopped
+        self._step_k = None         # the host's count is not the loaded optimiser's: read before the next step
         logging_func(f"Loading {name} model from last checkpoint ({start_epoch})...")
         return start_epoch + 1
 
@@ -919,20 +876,14 @@ class VariationalBaseModelVAE:
             rec = {"epoch": epoch, "Loss/Reconstruction Loss1": r1 / nb, "Loss/Reconstruction Loss2": r2 / nb,
                    "Loss/Reconstruction Loss1 hat": r1h / nb, "Loss/Reconstruction Loss2 hat": r2h / nb,
                    "Loss/Z1 KL Loss": k1 / nb, "Loss/Z2 KL Loss": k2 / nb, "Loss/Z KL Style": ks / nb}
-            if getattr(self, "grad_stats", None):       # gradient clipping on (FlatAdam.set_grad_clip): this epoch's norms
-                rec.update(self.grad_stats)
-            if getattr(self, "ema_stats", None):        # weight average on (FlatAdam.set_ema)
-                rec.update(self.ema_stats)
-            if getattr(self, "adv_stats", None):        # speaker adversary on (set_speaker_adversary)
-                rec.update(self.adv_stats)
-            if getattr(self, "factor_stats", None):     # factor penalty on (set_factor_penalty)
-                rec.update(self.factor_stats)
-            if getattr(self, "kl_stats", None):         # KL schedule on (set_kl_schedule)
-                rec.update(self.kl_stats)
-                if logs_path and self._is_rank0():
-                    # beside the logs directory: <log_dir>/kl_dims.json, this epoch's mean KL per latent dimension in nats
-                    with open(os.path.join(os.path.dirname(os.path.normpath(logs_path)), "kl_dims.json"), "w") as fp:
-                        json.dump(self.kl_dims, fp, indent=1)
+            # what train() left of the opt-in features that are on: gradient clipping, the weight average (FlatAdam.set_grad_clip,
+            # set_ema), the speaker adversary, the factor penalty, the KL schedule (set_speaker_adversary, ...)
+            for stats in (self.grad_stats, self.ema_stats, self.adv_stats, self.factor_stats, self.kl_stats):
+                rec.update(stats or {})
+            if self.kl_stats and logs_path and self._is_rank0():
+                # beside the logs directory: <log_dir>/kl_dims.json, this epoch's mean KL per latent dimension in nats
+                with open(os.path.join(os.path.dirname(os.path.normpath(logs_path)), "kl_dims.json"), "w") as fp:
+                    json.dump(self.kl_dims, fp, indent=1)
             ckpt_epoch = epoch % report_interval == 0 and bool(checkpoints_path)
             val = None
             if val_pairs is not None and self._is_rank0() and (epoch % max(1, int(val_interval)) == 0 or ckpt_epoch):
@@ -966,7 +917,7 @@ class VariationalBaseModelVAE:
                     gen = torch.cuda.default_generators[torch.device(self.device).index or 0]
                     osd["cuda_rng_seed"], osd["cuda_rng_offset"] = int(gen.initial_seed()), int(gen.get_offset())
                     torch.save(osd, base + ".opt")
-                    if getattr(self, "adversary", None) is not None:
+                    if self.adversary is not None:
                         # beside it: the speaker adversary (the .pth keeps the reference's keys)
                         torch.save({"config": dict(self.adv_config), "adversary": self.adversary.state_dict()},
                                    base + ".adv.pth")

@@ -40,6 +40,38 @@ _ALIGN = 4  # elements (16 bytes)
 _PAD = 32   # the flat buffers' length is a multiple of this: any world size up to 8 cuts it into 16-byte aligned shards
 
 
+class ScalarSender:
+    """Host -> device copies of a few floats that must not stall the host: a per-step schedule would wait behind a pageable
+    copy every step.  The values are staged in a small ring of PINNED slots (allocated on first use) and copied
+    asynchronously; a slot is reused only after the event recorded behind its last copies has completed.  Not capturable:
+    callers send before a capture / replay, never inside."""
+    SLOTS, WIDTH = 16, 8
+
+    def __init__(self):
+        self._ring, self._done, self._i = None, [None] * self.SLOTS, 0
+
+    def send(self, items):
+        """items: [(destination: a slice of a float32 device tensor, its values)], at most WIDTH values in all: one copy per
+        destination, one event behind them.  A destination that is not on a GPU is written plainly."""
+        if not items[0][0].is_cuda:
+            for dst, vals in items:
+                dst.copy_(torch.tensor(vals, dtype=torch.float32))
+            return
+        if self._ring is None:
+            self._ring = torch.empty(self.SLOTS, self.WIDTH, dtype=torch.float32, pin_memory=True)
+        i = self._i = (self._i + 1) % self.SLOTS
+        if self._done[i] is not None:
+            self._done[i].synchronize()
+        slot, o = self._ring[i], 0
+        for dst, vals in items:
+            for v in vals:
+                slot[o] = v
+                o += 1
+            dst.copy_(slot[o - len(vals):o], non_blocking=True)
+        self._done[i] = torch.cuda.Event()
+        self._done[i].record()
+
+
 class FlatAdam:
     def __init__(self, named_params: Iterable, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, layout=None):
         """layout: object with reference_layout(name, t) / storage_layout(name, t) (the model): how a tensor shaped like
@@ -81,7 +113,7 @@ class FlatAdam:
         # [t, 1-b1^t, sqrt(1-b2^t), -, lr, grad_scale, -, -]
         self.dev_state = torch.zeros(8, device=dev, dtype=torch.float32)
         self._dev_scalars = None           # (lr, grad_scale) as last written to dev_state[4:6]
-        self._pin, self._pin_ev, self._pin_i = None, None, 0      # pinned staging slots of sync_scalars
+        self._sender = ScalarSender()      # how sync_scalars writes them
         # gradient clipping / non-finite guard (set_grad_clip): off unless asked for
         # clip_state: [max_norm, norm, coef, grad_scale * coef, skip this step, skipped steps, clipped steps, not finite]
         self.max_norm, self.skip_nonfinite = None, True
@@ -168,38 +200,18 @@ class FlatAdam:
         send = self._dev_scalars != (lr, gs)
         send_clip = self.max_norm is not None and self._dev_max_norm != self.max_norm
         send_ema = self.ema_decay is not None and self._dev_ema != (self.ema_decay, self.ema_warmup)
-        if send or send_clip or send_ema:
-            if self.dev_state.is_cuda:
-                # staged through a small ring of PINNED slots, asynchronously: a per-step schedule must not stall the host
-                # behind a pageable copy every step; a slot is reused only after the copy that read it has completed
-                if self._pin is None:
-                    self._pin = torch.empty(16, 8, dtype=torch.float32, pin_memory=True)
-                    self._pin_ev = [None] * 16
-                i = self._pin_i = (self._pin_i + 1) % 16
-                if self._pin_ev[i] is not None:
-                    self._pin_ev[i].synchronize()
-                self._pin[i, 0], self._pin[i, 1] = lr, gs
-                if send:
-                    self.dev_state[4:6].copy_(self._pin[i, 0:2], non_blocking=True)
-                if send_clip:
-                    self._pin[i, 2] = self.max_norm
-                    self.clip_state[0:1].copy_(self._pin[i, 2:3], non_blocking=True)
-                if send_ema:        # [0] and [3] lie on either side of what the tick launch writes: 4 bytes each
-                    self._pin[i, 4], self._pin[i, 5] = self.ema_decay, float(self.ema_warmup)
-                    self.ema_state[0:1].copy_(self._pin[i, 4:5], non_blocking=True)
-                    self.ema_state[3:4].copy_(self._pin[i, 5:6], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                self._pin_ev[i] = ev
-            else:
-                self.dev_state[4:6].copy_(torch.tensor([lr, gs], dtype=torch.float32))
-                if send_clip:
-                    self.clip_state[0] = self.max_norm
+        items = []
+        if send:
+            items.append((self.dev_state[4:6], (lr, gs)))
             self._dev_scalars = (lr, gs)
-            if send_clip:
-                self._dev_max_norm = self.max_norm
-            if send_ema:
-                self._dev_ema = (self.ema_decay, self.ema_warmup)
+        if send_clip:
+            items.append((self.clip_state[0:1], (self.max_norm,)))
+            self._dev_max_norm = self.max_norm
+        if send_ema:            # [0] and [3] lie on either side of what the tick launch writes: 4 bytes each
+            items += [(self.ema_state[0:1], (self.ema_decay,)), (self.ema_state[3:4], (float(self.ema_warmup),))]
+            self._dev_ema = (self.ema_decay, self.ema_warmup)
+        if items:
+            self._sender.send(items)
 
     def set_grad_clip(self, max_norm=None, skip_nonfinite: bool = True):
         """Clip the global L2 norm of the whole gradient (grad_scale included: under data parallelism the averaged one) to

@@ -90,7 +90,7 @@ def main():
         pairs += [("buffer " + n, u, v) for (n, u), (_, v) in zip(a.model.named_buffers(), b.model.named_buffers())]
         out["same"] = {n: bool(torch.equal(u, v)) for n, u, v in pairs}
         out["max_norm"] = max_norm
-        out["fac_k"], out["kl_k"] = [a._fac_k, b._fac_k], [a._kl_k, b._kl_k]
+        out["step_k"] = [a._step_k, b._step_k]
         out["clipped"] = [a.optimizer.grad_clip_stats()["clipped"], b.optimizer.grad_clip_stats()["clipped"]]
         out["skipped"] = [a.optimizer.grad_clip_stats()["skipped"], b.optimizer.grad_clip_stats()["skipped"]]
     print("DDPCHILD " + json.dumps(out), flush=True)

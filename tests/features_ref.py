@@ -6,7 +6,7 @@ runs it on the CPU, tests/test_hip_all_features.py uses it on the MI355X.
 """
 import numpy as np
 
-# the configuration `all_on` switches on unless told otherwise; the three warm-ups differ on purpose: the three host counters
+# the configuration `all_on` switches on unless told otherwise; the three warm-ups differ on purpose: the three weights
 # saturate at different steps
 KL = dict(kind="linear", start=1.0, steps=6)
 ADV = dict(weight=0.5, hidden=64, warmup_steps=5)

@@ -494,3 +494,21 @@ def test_zero_grad_scale_is_honoured_and_none_keeps_the_last():
         assert not same_bits(before["p"], after["p"])
     opt.step(grad_scale=1.0)
     assert float(opt.dev_state[5]) == 1.0
+
+
+def test_scalar_sender_keeps_every_pair_through_the_ring_wrap():
+    """optim.ScalarSender on its own: 40 sends of 40 distinct pairs to one 2-float device buffer, a clone of the buffer enqueued
+    behind each, ONE synchronise at the end.  The ring has 16 pinned slots, so send 17 reuses the slot of send 1 while copies
+    are still in flight: a slot overwritten before its copy had read it would show as a later pair in an earlier clone."""
+    from dvae_amd.optim import ScalarSender
+    sender, buf = ScalarSender(), torch.zeros(2, device=DEV, dtype=torch.float32)
+    assert sender.SLOTS == 16 and sender.WIDTH >= 8
+    pairs = [(float(i) + 0.5, -3.0 * i - 1.0) for i in range(40)]
+    assert len(set(pairs)) == 40
+    clones = []
+    for pair in pairs:
+        sender.send([(buf[0:2], pair)])
+        clones.append(buf.clone())
+    torch.cuda.synchronize()
+    got = [tuple(c.tolist()) for c in clones]
+    assert got == pairs, [(i, g, p) for i, (g, p) in enumerate(zip(got, pairs)) if g != p]

@@ -79,7 +79,7 @@ def test_warmup_under_one_graph_equals_eager(feed):
     assert graphs[0] is None and graphs[1] is not None and all(g is graphs[1] for g in graphs[1:])
     want = [float(np.float32(0.5 * min(1.0, k / 5))) for k in range(8)]
     assert ca == want and cb == want and len(set(want)) == 6
-    assert a._adv_k == b._adv_k == 8 and a.adversary.optimizer.t == 8
+    assert a._step_k == b._step_k == 8 and a.adversary.optimizer.t == 8
     # the first step ran under weight 0: the model's loss vector is the monitor's; later the encoder has been pushed
     assert la[0] == lz[0] and la[1] == lz[1]          # (step 1's weights moved under lambda = 0 as well)
     assert any(u != v for u, v in zip(la[2:], lz[2:]))

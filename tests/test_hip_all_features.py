@@ -1,8 +1,8 @@
 """The training step with EVERY opt-in feature on together, on the MI355X: gradient clipping with the non-finite guard, the
 weight average, the KL schedule with free bits, the speaker adversary and the factor penalty (DESIGN.md sections 4.9, 4.10, 4.16,
 4.18, 4.19).  Each has a train suite of its own that checks it alone; here the code that makes them coexist runs: the three-root
-backward, the three host counters and their device scalars under ONE captured graph, the adversary's own guard beside a skipped
-step, the packing of train()'s single copy, and a checkpoint that restores all of it in one pass.  The step is bit-deterministic
+backward, the host's step count and the three features' device scalars under ONE captured graph, the adversary's own guard beside
+a skipped step, train()'s single named copy, and a checkpoint that restores all of it in one pass.  The step is bit-deterministic
 in the default mode (tests/test_hip_determinism.py), so all but one test compare bits; the whole-model gradient is held to
 float64 restatements of the two extra roots within tests/test_hip_model.py's tolerances.
 
@@ -135,8 +135,8 @@ def test_graph_equals_eager_all_on(feed, probe):
     # one capture (at the second step) serves all three weights while they change
     assert graphs[0] is None and graphs[1] is not None and all(g is graphs[1] for g in graphs[1:])
     assert len({F.expected_coefficients(cfg, k) for k in range(8)}) == 8
-    assert a._kl_k == a._adv_k == a._fac_k == a.optimizer.t == a.adversary.optimizer.t == 8
-    assert b._kl_k == b._adv_k == b._fac_k == b.optimizer.t == b.adversary.optimizer.t == 8
+    assert a._step_k == a.optimizer.t == a.adversary.optimizer.t == 8
+    assert b._step_k == b.optimizer.t == b.adversary.optimizer.t == 8
     st = a.optimizer.clip_state.tolist()
     assert st[6] >= 1 and st[5] == 0, st
     assert a.optimizer.ema_state[1].item() == 8
@@ -315,7 +315,7 @@ def test_whole_model_gradient_is_the_sum_of_its_three_roots(feed, probe):
 def test_skipped_step_with_everything_on(feed, probe):
     """A non-finite model gradient on the fourth of eight steps: the model's optimiser, its average and its step count keep
     every bit; the adversary's gradient was finite and its optimiser, which guards only itself (DESIGN.md section 4.18), steps;
-    the three schedule positions are set right from the step count and the skipped step's weights are repeated."""
+    the schedules' position is set right from the step count and the skipped step's weights are repeated."""
     w = make_trainer(B, T)
     cfg = on(w, probe)
     opt, adv = w.optimizer, w.adversary.optimizer
@@ -345,11 +345,11 @@ def test_skipped_step_with_everything_on(feed, probe):
     assert st[5] == skipped + 1 and st[7] == 1.0 and st[4] == 1.0, st
     assert adv.max_norm == float("inf") and adv.skip_nonfinite          # _sync_adv_guard gave it a guard of its own
     assert adv.t == 4 and not dev_equal(adv.flat_p, adv_p) and adv.clip_state[5].item() == 0.0
-    assert w._kl_k == w._adv_k == w._fac_k == 3
+    assert w._step_k == 3
     losses.append(one_step(w, feed, 4))
     assert coefs(w) == F.expected_coefficients(cfg, 3)              # ... which step 5 repeats: it is Adam step 4
     assert opt.dev_state[0].item() == 4 and opt.clip_state[7].item() == 0.0
-    assert opt.ema_state[1].item() == 4 and w._kl_k == w._adv_k == w._fac_k == 4
+    assert opt.ema_state[1].item() == 4 and w._step_k == 4
     more, _ = run(w, feed, 3, start=5)
     losses += more
     assert coefs(w) == F.expected_coefficients(cfg, 6)
@@ -359,12 +359,48 @@ def test_skipped_step_with_everything_on(feed, probe):
     assert bool(torch.isfinite(opt.ema).all())
 
 
+def test_a_feature_switched_on_after_an_unseen_skip_puts_every_weight_at_the_true_position(feed, probe):
+    """Only the KL schedule (and the non-finite guard) on; three steps through step_async, which reads nothing back, the second
+    with a non-finite gradient: the host's count says 3, the optimiser's 2.  set_factor_penalty then forgets the host's count,
+    so the next step runs BOTH features under the weights of position optimizer.t as read before it.  (With a counter per
+    feature the penalty alone read t and the schedule kept the host's 3.)"""
+    data, noise, _ = feed
+    w = make_trainer(B, T)
+    cfg = on(w, probe, adv=None, factor=None, ema=None, max_norm=float("inf"))
+    opt = w.optimizer
+    plain_step = opt.step
+
+    def poked_step(grad_scale=1.0):
+        opt.flat_g[5] = float("inf")
+        return plain_step(grad_scale=grad_scale)
+
+    def go(i):
+        w.model.eps_override = noise[(2 * i) % 3]
+        opt.step = poked_step if i == 1 else plain_step
+        out = w.step_async(*data[i % 3], None)
+        opt.step = plain_step
+        return out
+
+    for i in range(3):
+        go(i)
+    assert w._step_k == 3                           # the host has not looked
+    w.set_factor_penalty(F.FACTOR["tc_weight"], F.FACTOR["shared_weight"], warmup_steps=F.FACTOR["warmup_steps"])
+    cfg["factor"] = dict(F.FACTOR)
+    t = opt.t
+    assert t == 2 and opt.clip_state[5].item() == 1.0
+    want, host = F.expected_coefficients(cfg, t), F.expected_coefficients(cfg, 3)
+    assert want[0] != host[0] and want[2] != host[2]            # the two positions differ in both features' weights
+    last = go(3)
+    assert coefs(w) == want, (coefs(w), want, host)
+    assert w._step_k == 3 and opt.t == 3 and all(math.isfinite(v) for v in last.tolist())
+
+
 # ------------------------------------------------------------------ F
 @pytest.mark.parametrize("clip,ema", [(True, True), (True, False), (False, True)], ids=["clip+ema", "clip", "ema"])
 def test_train_reports_every_record_with_everything_on(feed, probe, clip, ema):
-    """train()'s one device-to-host copy is packed by index arithmetic that depends on which of schedule, clipping and the
-    average are on; the adversary's and the penalty's sums ride beside it.  Every reported value against the per-step values,
-    by train()'s own formulas, accumulated in its order in float64: exactly."""
+    """train()'s one device-to-host copy carries whichever of the schedule's, the adversary's, the penalty's, clipping's and the
+    average's running tensors are on, by name.  Every reported value against the per-step values, by train()'s own formulas,
+    accumulated in its order in float64: exactly."""
     data, _, spk = feed
     w = make_trainer(B, T)
     kw = {}
@@ -393,7 +429,7 @@ def test_train_reports_every_record_with_everything_on(feed, probe, clip, ema):
     loader = [(x1.cpu(), x2.cpu(), spk[i]) for i, (x1, x2) in enumerate(data)] * 2          # six steps
     got = w.train(loader, 1, logging_func=lambda *_: None)
     n = 6
-    assert len(seen) == n and w._kl_k == w._adv_k == w._fac_k == opt.t == n and w.adversary.optimizer.t == n
+    assert len(seen) == n and w._step_k == opt.t == n and w.adversary.optimizer.t == n
 
     def total(key):
         tot = np.zeros_like(seen[0][key])
@@ -442,8 +478,8 @@ def test_train_reports_every_record_with_everything_on(feed, probe, clip, ema):
 
 # ------------------------------------------------------------------ G
 def test_state_round_trip_all_on(feed, probe, tmp_path):
-    """`b` is fresh and takes the four states as objects; `c` has already stepped — its three host counters hold a position —
-    and takes them from the files run_training writes, through load_last_model, which has to forget all three."""
+    """`b` is fresh and takes the four states as objects; `c` has already stepped — its host count holds a position — and takes
+    them from the files run_training writes, through load_last_model, which has to forget it."""
     a = make_trainer(B, T)
     cfg = on(a, probe)
     run(a, feed, 3)
@@ -457,7 +493,7 @@ def test_state_round_trip_all_on(feed, probe, tmp_path):
     b.model.load_state_dict(saved["model"])
     b.adversary.load_state_dict(saved["adv"])
     b.optimizer.load_state_dict(saved["opt"])
-    b._kl_k = b._adv_k = b._fac_k = None
+    b._step_k = None
     with b.ema_weights():
         now = b.model.state_dict()
         assert all(dev_equal(now[k], saved["ema"][k]) for k in saved["ema"])
@@ -469,9 +505,9 @@ def test_state_round_trip_all_on(feed, probe, tmp_path):
     c = make_trainer(B, T)
     assert on(c, probe) == cfg
     run(c, feed, 1)
-    assert c._kl_k == c._adv_k == c._fac_k == 1
+    assert c._step_k == 1
     assert c.load_last_model(str(tmp_path), logging_func=lambda *_: None) == 2
-    assert c._kl_k is None and c._adv_k is None and c._fac_k is None and c.optimizer.t == c.adversary.optimizer.t == 3
+    assert c._step_k is None and c.optimizer.t == c.adversary.optimizer.t == 3
     la, _ = run(a, feed, 3, start=3)
     for w, who in ((b, "from the objects"), (c, "from the files, after a step of its own")):
         lw, _ = run(w, feed, 3, start=3)
@@ -482,7 +518,7 @@ def test_state_round_trip_all_on(feed, probe, tmp_path):
         assert dev_equal(a.optimizer.ema, w.optimizer.ema) and dev_equal(a.optimizer.ema_state, w.optimizer.ema_state), who
         assert dev_equal(a._kl_coef, w._kl_coef) and dev_equal(a._adv_coef, w._adv_coef) and dev_equal(a._fac_coef, w._fac_coef), who
         assert coefs(w) == F.expected_coefficients(cfg, 5), who
-        assert w._kl_k == w._adv_k == w._fac_k == w.optimizer.t == w.adversary.optimizer.t == 6, who
+        assert w._step_k == w.optimizer.t == w.adversary.optimizer.t == 6, who
         assert_same_buffers(a, w, who)
 
 

@@ -82,7 +82,7 @@ def test_ddp_step_with_the_features_on_equals_the_plain_step_bitwise():
     assert all(o["same"].values()), [n for n, v in o["same"].items() if not v]
     assert o["stats"]["finish"] == 0 and o["stats"]["hook"] == 5 * o["buckets"], o["stats"]
     assert min(o["clipped"]) >= 1 and o["skipped"] == [0, 0], (o["clipped"], o["skipped"], o["max_norm"])
-    assert o["t"] == [5, 5] and o["fac_k"] == [5, 5] and o["kl_k"] == [5, 5] and o["views_intact"]
+    assert o["t"] == [5, 5] and o["step_k"] == [5, 5] and o["views_intact"]
 
 
 # ----------------------------------------------------------------------------------------------------------------------

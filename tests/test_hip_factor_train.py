@@ -101,7 +101,7 @@ def test_warm_up_under_one_graph_equals_eager(feed):
     want = [[float(np.float32(v)) for v in a.factor_weights_at(k)] for k in range(8)]
     assert [c[0] for c in ca] == want
     assert [w[0] for w in want] == [float(np.float32(3.0 * min(1.0, k / 5))) for k in range(8)] and want[5] == [3.0, 1.5]
-    assert a.optimizer.t == b.optimizer.t == 8 and a._fac_k == 8
+    assert a.optimizer.t == b.optimizer.t == 8 and a._step_k == 8
     # the penalty the kernel reports is the weights' combination of its own statistics
     for (wt, ws), aux in ca:
         assert math.isclose(aux[4], wt * (aux[0] + aux[1]) + ws * aux[2], rel_tol=1e-5, abs_tol=1e-6)
@@ -195,7 +195,7 @@ def test_train_reports_what_the_steps_add_up_to(feed):
     w.step_async = recording
     loader = [(x1.cpu(), x2.cpu(), torch.zeros(B, dtype=torch.int64)) for x1, x2 in data] * 2          # six steps
     w.train(loader, 1, logging_func=lambda *_: None)
-    assert len(seen) == 6 and w.optimizer.t == 6 and w._fac_k == 6
+    assert len(seen) == 6 and w.optimizer.t == 6 and w._step_k == 6
     tot = np.sum(seen, axis=0)
     st = w.factor_stats
     assert set(st) == FACTOR_KEYS
@@ -215,7 +215,7 @@ def test_the_configuration_rides_in_the_optimiser_state(feed):
     b.set_factor_penalty(2.0, 0.5, warmup_steps=6)
     b.optimizer.load_state_dict(sd)                                         # the same configuration: accepted
     b.model.load_state_dict(a.model.state_dict())
-    b._fac_k = None
+    b._step_k = None
     la, _ = run(a, feed, 2)
     lb, _ = run(b, feed, 2)                                                 # ... and continued where the other one is
     assert la == lb and b._fac_coef.tolist() == a._fac_coef.tolist() == [float(np.float32(v)) for v in a.factor_weights_at(3)]

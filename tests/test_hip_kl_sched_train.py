@@ -68,7 +68,7 @@ def test_linear_ramp_under_one_graph_equals_eager(feed):
     assert graphs[0] is None and graphs[1] is not None and all(g is graphs[1] for g in graphs[1:])
     want = [[10.0, float(np.float32(a.kl_weight_at(k)))] for k in range(8)]
     assert ca == want and cb == want and [w[1] for w in want[:6]] == [0.0, 2.0, 4.0, 6.0, 8.0, 10.0]
-    assert a.optimizer.t == b.optimizer.t == 8 and a._kl_k == 8
+    assert a.optimizer.t == b.optimizer.t == 8 and a._step_k == 8
     # the first step's weight is 0: LOSS is mse_cof times the four L1 terms of its own vector, exactly
     l0 = [np.float32(v) for v in la[0]]
     assert np.float32(la[0][0]) == np.float32(10.0) * (((l0[1] + l0[2]) + l0[3]) + l0[4])
@@ -111,7 +111,7 @@ def test_train_reports_what_the_steps_add_up_to(feed):
     loader = [(x1.cpu(), x2.cpu(), torch.zeros(B, dtype=torch.int64)) for x1, x2 in data] * 2          # six steps
     lines = []
     w.train(loader, 1, logging_func=lines.append)
-    assert len(seen) == 6 and w.optimizer.t == 7 and w._kl_k == 7
+    assert len(seen) == 6 and w.optimizer.t == 7 and w._step_k == 7
     tot = np.zeros(2 + 2 * D)
     for a in seen:
         tot += a[2:4 + 2 * D]
@@ -136,7 +136,7 @@ def test_the_schedule_rides_in_the_optimiser_state(feed):
     b.optimizer.load_state_dict(sd)                                         # the same schedule: accepted
     assert b.optimizer.t == 2
     b.model.load_state_dict(a.model.state_dict())
-    b._kl_k = None
+    b._step_k = None
     la, _ = run(a, feed, 2)
     data, noise = feed
     lb = []

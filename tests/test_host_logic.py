@@ -512,6 +512,22 @@ def test_sync_scalars_honours_a_zero_grad_scale_and_none_keeps_the_last():
     assert sent() == (0.5, 1.0)
 
 
+def test_named_to_host_gives_every_name_its_own_list_back():
+    """train()'s end-of-epoch copy: named tensors of different lengths and float types go out as ONE float64 concatenation
+    and come back cut by name, in order, each value the exact double of what went in."""
+    from dvae_amd.model.variational_base_vae import named_to_host
+    parts = {"loss": torch.arange(8, dtype=torch.float64) / 3.0,
+             "gmax": torch.tensor([2.5e30], dtype=torch.float32),
+             "kl": torch.arange(1, 12, dtype=torch.float64) * 1e-7,
+             "t": torch.tensor([16777216.0], dtype=torch.float32)}
+    got = named_to_host(parts)
+    assert list(got) == list(parts)
+    for name, t in parts.items():
+        assert got[name] == t.double().tolist(), name
+    assert [len(v) for v in got.values()] == [8, 1, 11, 1]
+    assert named_to_host({"only": torch.zeros(3)}) == {"only": [0.0, 0.0, 0.0]}
+
+
 def test_shared_gpu_decision_needs_local_world_size(monkeypatch):
     """WORLD_SIZE counts the ranks of every node; only LOCAL_WORLD_SIZE may switch the persistent recurrences off."""
     import dvae_amd  # noqa: F401
