@@ -156,6 +156,9 @@ SIGNATURES = {
     "dvae_modspec_windows": (i32, [vp, i32, i32, i32, vp, vp, vp]),
     "dvae_modspec_group_sum": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp]),
     "dvae_modspec_filter": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp]),
+    "dvae_msloss_ws_bytes": (i64, [i32, i32]),
+    "dvae_msloss_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp]),
+    "dvae_msloss_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp]),
     "dvae_set_compute_mode": (i32, [i32]),
     "dvae_get_compute_mode": (i32, []),
     "dvae_set_deterministic": (i32, [i32]),

@@ -1550,3 +1550,4 @@ DVAE_API int dvae_conv_unpack_add_w(const float* dWp, float* dW, int Cout, int C
 
 // ---- global variance, modulation spectrum and its postfilter: the kernels of modspec.hip, part of this translation unit
 #include "modspec.hip"
+#include "msloss.hip"       // the modulation-spectrum / global-variance loss of the train step: the same

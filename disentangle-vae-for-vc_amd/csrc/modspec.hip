@@ -24,12 +24,12 @@ struct MsTile {
   double mean[MS_BINS];
 };
 
-// frames of bins [c0, c0 + nb) of one window -> centred float64 frames in LDS.  mean: lane j of a bin's 16 adds frames j,
-// j + 16, ... in index order, then a fixed xor tree over the 16 (they lie in one wave).
-__device__ __forceinline__ void ms_stage(const float* __restrict__ win, int nb, int D, const double* __restrict__ twiddle,
-                                         MsTile& s) {
+// frames of bins [c0, c0 + nb) of one window (bin b at win + b ld) -> centred float64 frames in LDS.  mean: lane j of a bin's
+// 16 adds frames j, j + 16, ... in index order, then a fixed xor tree over the 16 (they lie in one wave).
+__device__ __forceinline__ void ms_stage(const float* __restrict__ win, int64_t ld, int nb, int D,
+                                         const double* __restrict__ twiddle, MsTile& s) {
   const int tid = threadIdx.x;
-  for (int i = tid; i < nb * D; i += MS_THREADS) s.d[i / D][i % D] = (double)win[i];
+  for (int i = tid; i < nb * D; i += MS_THREADS) s.d[i / D][i % D] = (double)win[(i / D) * ld + i % D];
   for (int i = tid; i < 2 * D; i += MS_THREADS) s.tw[i >> 1][i & 1] = twiddle[i];
   __syncthreads();
   const int b = tid / MS_SEG, j = tid % MS_SEG;
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(MS_THREADS) modspec_windows_kernel(const float
                                                                      float* __restrict__ rows) {
   __shared__ MsTile s;
   const int w = blockIdx.x, c0 = blockIdx.y * MS_BINS, nb = min(MS_BINS, C - c0), H = D / 2;
-  ms_stage(windows + ((int64_t)w * C + c0) * D, nb, D, twiddle, s);
+  ms_stage(windows + ((int64_t)w * C + c0) * D, D, nb, D, twiddle, s);
   for (int i = threadIdx.x; i < nb * H; i += MS_THREADS) {
     const int b = i / H, k = i % H + 1;
     double re, im;
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(MS_THREADS) modspec_filter_kernel(const float*
   __shared__ MsTile s;
   __shared__ double Y[MS_BINS][MS_DMAX / 2][2];
   const int w = blockIdx.x, c0 = blockIdx.y * MS_BINS, nb = min(MS_BINS, C - c0), H = D / 2;
-  ms_stage(windows + ((int64_t)w * C + c0) * D, nb, D, twiddle, s);
+  ms_stage(windows + ((int64_t)w * C + c0) * D, D, nb, D, twiddle, s);
   for (int i = threadIdx.x; i < nb * H; i += MS_THREADS) {
     const int b = i / H, k = i % H + 1;
     double re, im;

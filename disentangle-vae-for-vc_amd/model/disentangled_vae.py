@@ -242,6 +242,9 @@ class DisentangledVAE(nn.Module):
         # True: forward_full(train=True) leaves aliases of (z, q_mu, q_lv) in `factor_inputs` for the trainer's factor penalty
         self.factor_tap = False
         self.factor_inputs = None
+        # likewise an alias of rec_hat in `smooth_inputs` for the trainer's smoothing penalty
+        self.smooth_tap = False
+        self.smooth_inputs = None
 
     # ---- parameters in the order their gradients complete during backward (for bucketed all-reduce)
     def backward_param_order(self):
@@ -454,6 +457,12 @@ class DisentangledVAE(nn.Module):
                                             w16=[self._w16(f"postnet.{i}") for i in range(5)])
         rec = FramesToMelFn.apply(y, N, N_MEL, T)
         rec_hat = FramesToMelFn.apply(y_hat, N, N_MEL, T)
+        self.smooth_inputs = None
+        if self.smooth_tap and train:
+            # the smoothing penalty (ConvolutionalMulVAE.set_smoothing_penalty) is a second consumer of rec_hat: the trainer
+            # applies it to this alias, and the two gradients are summed by one launch (ops.FanoutFn)
+            rec_hat, rec_hat_s = fanout(rec_hat, 2)
+            self.smooth_inputs = (rec_hat_s,)
         return rec, rec_hat, q_mu, q_lv, s_mu, s_lv
 
     def forward(self, x1, x2, train=True):
@@ -649,6 +658,52 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         opt.factor_penalty = dict(self.factor_cfg)      # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
         self._feature_set("factor")
         self.factor_weights = self.factor_stats = None
+
+    def set_smoothing_penalty(self, ms_weight=None, gv_weight=0.0, *, window=None, floor=0.003, warmup_steps=0):
+        """The modulation-spectrum and global-variance loss on rec_hat of every TRAINING step, inside the replayed graph
+        (ops.SmoothingPenaltyFn, csrc/msloss.hip): LOSS + ms_weight L_ms + gv_weight L_gv, the squared
+        distance between the log modulation spectra (disjoint windows of `window` frames, default min(64, T); nats^2) and between
+        the log global variances of rec_hat and of the input it reconstructs, each logarithm stabilised by `floor` (0.003: 0.3 dB
+        of the normalised 100 dB range; a setting, not a measured optimum).
+        ms_weight: None (off: the step launches what it launched without this, under the same graph signature) or >= 0; (0, 0)
+        is a live monitor: the statistics are computed, the model's step keeps its bits.  The effective weights at the
+        optimiser's step count k are w min(1, k / warmup_steps): two device scalars refreshed by one small copy before the step,
+        never a new capture.  The eight reported scalars, LOSS included, stay the reference's; `smooth_aux` (float[5] on the
+        device: L_ms, L_gv, msd_db, gv_ratio_db, penalty) holds the statistics of the last step and `train()` reports their
+        means as Smooth/... in `smooth_stats`.  Validation, `Val/Loss` and checkpoints/best.json do not see the penalty.
+        Data parallel: every rank penalises its LOCAL rows with the same weights; nothing is exchanged (not run on more than
+        one GPU)."""
+        opt = self.optimizer
+        if ms_weight is None:
+            self.smooth_cfg = None
+            self.model.smooth_tap = False
+            opt.smoothing_penalty = None
+            return
+        try:
+            ms_weight, gv_weight, floor, warmup_steps = float(ms_weight), float(gv_weight), float(floor), int(warmup_steps)
+            window = None if window is None else int(window)
+        except (TypeError, ValueError):
+            raise ValueError("set_smoothing_penalty: ms_weight, gv_weight and floor are numbers, window and warmup_steps integers")
+        if not (ms_weight >= 0.0 and math.isfinite(ms_weight) and gv_weight >= 0.0 and math.isfinite(gv_weight)) \
+                or warmup_steps < 0:
+            raise ValueError(f"set_smoothing_penalty: ms_weight {ms_weight} and gv_weight {gv_weight} must be finite and >= 0, "
+                             f"warmup_steps {warmup_steps} >= 0")
+        if not (floor > 0.0 and math.isfinite(floor) and floor * floor > 0.0):
+            raise ValueError(f"set_smoothing_penalty: the floor {floor} must be positive and finite")
+        from .. import ops
+        window = ops.msloss_window(self.model.n_frames, window)      # ValueError: odd, out of range, no divisor of T
+        dev = opt.flat_p.device
+        if dev.type != "cuda":
+            raise RuntimeError("set_smoothing_penalty: the penalty runs only on the HIP device (no CPU fallback)")
+        if self._smooth_coef is None:   # allocated once: a captured graph holds their addresses
+            self._smooth_coef = torch.zeros(2, device=dev, dtype=torch.float32)
+            self.smooth_aux = torch.zeros(5, device=dev, dtype=torch.float32)
+        ops.msloss_twiddle(window, dev)     # the device table of this window: allocated here, outside any capture
+        self.smooth_cfg = dict(ms_weight=ms_weight, gv_weight=gv_weight, window=window, floor=floor, warmup_steps=warmup_steps)
+        self.model.smooth_tap = True
+        opt.smoothing_penalty = dict(self.smooth_cfg)   # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
+        self._feature_set("smooth")
+        self.smooth_weights = self.smooth_stats = None
 
     def kl_weight_at(self, k, epoch=1):
         """The KL weight of the step that runs after `k` optimiser steps, in epoch `epoch` (kl_schedule.KLSchedule)."""

@@ -70,15 +70,17 @@ class VariationalBaseModelVAE:
         self._graph = None
         self._graph_sig = None
         self._graph_calls = 0
-        # the opt-in features of the train step (the subclass's set_kl_schedule / set_speaker_adversary / set_factor_penalty):
+        # the opt-in features of the train step (the subclass's set_kl_schedule / set_speaker_adversary / set_factor_penalty /
+        # set_smoothing_penalty):
         # None is "off".  Their weights at optimiser step k are device scalars, sent before the step by _sync_step_coefs
-        self.kl_sched = self.adversary = self.adv_config = self.factor_cfg = None
-        self.kl_weight = self.adv_weight = self.factor_weights = None      # as last computed for a step (float, float, pair)
+        self.kl_sched = self.adversary = self.adv_config = self.factor_cfg = self.smooth_cfg = None
+        self.kl_weight = self.adv_weight = self.factor_weights = self.smooth_weights = None      # as last computed for a step
         self.kl_stats = self.kl_dims = self.adv_stats = self.factor_stats = self.grad_stats = self.ema_stats = None
+        self.smooth_stats = None
         self.adv_out = self.adv_pred = None
         self._step_k = None         # the host's count of optimizer.t (None: read it before the next step)
         self._kl_epoch = 1
-        self._kl_coef = self._adv_coef = self._fac_coef = None      # the device scalars: allocated once, by the setters
+        self._kl_coef = self._adv_coef = self._fac_coef = self._smooth_coef = None      # the device scalars: allocated once, by the setters
         self._coef_sent = {}        # feature -> the weights its device scalars hold
         self._sender = ScalarSender()
         self._loss_seed = None
@@ -145,7 +147,7 @@ class VariationalBaseModelVAE:
                 int(self.batch_size), bool(self.model.training),
                 self.reducer is not None, getattr(self.reducer, "world_size", 1), ops.current_mode(),
                 bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature() + kl + self._adv_signature() \
-            + self._factor_signature()
+            + self._factor_signature() + self._smooth_signature()
 
     def _adv_signature(self):
         """The speaker adversary on/off and its shape change the launches of a step; its weight does not (a device scalar,
@@ -157,6 +159,19 @@ class VariationalBaseModelVAE:
         """The factor penalty on/off changes the launches of a step; its two weights and their warm-up do not (device scalars,
         _sync_step_coefs).  Nothing is added while it is off."""
         return (("factor",),) if self.factor_cfg is not None else ()
+
+    def _smooth_signature(self):
+        """The smoothing penalty on/off, its window and its floor change the launches of a step (both are kernel arguments); its
+        two weights and their warm-up do not (device scalars, _sync_step_coefs).  Nothing is added while it is off."""
+        cfg = self.smooth_cfg
+        return (("smooth", cfg["window"], cfg["floor"]),) if cfg is not None else ()
+
+    def smooth_weights_at(self, k):
+        """(w_ms, w_gv) of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
+        cfg = self.smooth_cfg
+        n = int(cfg["warmup_steps"])
+        f = 1.0 if n <= 0 else min(1.0, k / n)
+        return float(cfg["ms_weight"]) * f, float(cfg["gv_weight"]) * f
 
     def factor_weights_at(self, k):
         """(w_tc, w_sh) of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
@@ -172,17 +187,17 @@ class VariationalBaseModelVAE:
         return w if n <= 0 else w * min(1.0, k / n)
 
     def _feature_set(self, feature):
-        """A setter switched `feature` ("kl", "adv", "factor") on or reconfigured it: its device scalars are sent afresh, and
+        """A setter switched `feature` ("kl", "adv", "factor", "smooth") on or reconfigured it: its device scalars are sent afresh, and
         every feature takes the optimiser's true step count at the next step (one read of FlatAdam.t)."""
         self._coef_sent.pop(feature, None)
         self._step_k = None
 
     def _sync_step_coefs(self):
         """Host -> device copy of the weights of the step about to run, for every feature that is on and whose weights changed
-        since its last copy: (mse_cof, KL weight) of a schedule, the adversary's reversal weight, the penalty's pair.  Beside
+        since its last copy: (mse_cof, KL weight) of a schedule, the adversary's reversal weight, the pair of either penalty.  Beside
         optimizer.sync_scalars, never inside a capture.  The step about to run is number `_step_k` by the host's ONE count,
         which starts from FlatAdam.t (one read) and is set right from it wherever the host reads the device anyway."""
-        if self.kl_sched is None and self.adversary is None and self.factor_cfg is None:
+        if self.kl_sched is None and self.adversary is None and self.factor_cfg is None and self.smooth_cfg is None:
             return              # the plain trainer: no read of optimizer.t (a device-to-host sync), no count
         if self._step_k is None:
             self._step_k = self.optimizer.t
@@ -196,6 +211,9 @@ class VariationalBaseModelVAE:
         if self.factor_cfg is not None:
             self.factor_weights = self.factor_weights_at(k)
             want["factor"] = (self._fac_coef, self.factor_weights)
+        if self.smooth_cfg is not None:
+            self.smooth_weights = self.smooth_weights_at(k)
+            want["smooth"] = (self._smooth_coef, self.smooth_weights)
         send = {f: bv for f, bv in want.items() if self._coef_sent.get(f) != bv[1]}
         if send:
             # through the ring of pinned slots (optim.ScalarSender): a per-step schedule must not stall the host
@@ -210,7 +228,7 @@ class VariationalBaseModelVAE:
         if adv is not None:
             self._sync_adv_guard()              # may allocate the buffers of the adversary's non-finite guard
             adv.optimizer.sync_scalars(1.0)     # after the first step nothing: its step() sends the same value
-        if adv is not None or self.factor_cfg is not None:
+        if adv is not None or self.factor_cfg is not None or self.smooth_cfg is not None:
             from .. import ops
             ops.unit_seed(dev)                  # allocated outside the capture
         self._sync_step_coefs()
@@ -273,7 +291,7 @@ class VariationalBaseModelVAE:
 
     def _train_step_body(self, data1, data2, labels2=None):
         self.optimizer.zero_grad()
-        adv, fac = self.adversary, self.factor_cfg
+        adv, fac, smo = self.adversary, self.factor_cfg, self.smooth_cfg
         unsplit = hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full")
         outs = None
         if adv is not None:
@@ -286,6 +304,8 @@ class VariationalBaseModelVAE:
             adv.optimizer.zero_grad()       # store-first parameters only: no launch, the written-once counts start over
         if fac is not None and not unsplit:
             raise RuntimeError("the factor penalty needs the unsplit forward (forward_full / losses_vector_full)")
+        if smo is not None and not unsplit:
+            raise RuntimeError("the smoothing penalty needs the unsplit forward (forward_full / losses_vector_full)")
         if unsplit:
             # the eight scalars as one vector (fused loss kernels) on the UNSPLIT outputs; backward is seeded with the
             # constant (1, 0, ..., 0): `vec[0].backward()` and the reference's ten output slices cost ~25 zero-fill /
@@ -310,6 +330,15 @@ class VariationalBaseModelVAE:
                 pen = ops.FactorPenaltyFn.apply(*self.model.factor_inputs, self.model.speaker_size, self._fac_coef,
                                                 self.factor_aux)
                 self.model.factor_inputs = None
+                roots.append(pen)
+                seeds.append(ops.unit_seed(vec.device))
+            if smo is not None:
+                # LOSS + penalty: the penalty reads the alias forward_full left of rec_hat, the step's two inputs as its targets
+                # and the two weights on the device; ONE backward adds its gradient to the loss's (ops.FanoutFn: one sum)
+                from .. import ops
+                pen = ops.SmoothingPenaltyFn.apply(*self.model.smooth_inputs, data1, data2, smo["window"], smo["floor"],
+                                                   self._smooth_coef, self.smooth_aux)
+                self.model.smooth_inputs = None
                 roots.append(pen)
                 seeds.append(ops.unit_seed(vec.device))
             if adv is not None:
@@ -429,7 +458,8 @@ class VariationalBaseModelVAE:
 
     # ---- variational_base_vae.py:58-70
     def step(self, data1, data2, speaker_ids, train=False):
-        if train and (self.kl_sched is not None or self.adversary is not None or self.factor_cfg is not None):
+        if train and (self.kl_sched is not None or self.adversary is not None or self.factor_cfg is not None
+                      or self.smooth_cfg is not None):
             # the same one copy carries the optimiser's step count: the schedules' position is exactly t (a skipped step)
             vec = torch.cat([self.step_async(data1, data2, speaker_ids), self.optimizer.dev_state[0:1]]).tolist()
             self._step_k = int(vec[8])
@@ -471,8 +501,9 @@ class VariationalBaseModelVAE:
         opt = self.optimizer
         clip = getattr(opt, "max_norm", None) is not None
         ema = getattr(opt, "ema_decay", None) is not None
-        sched, adv, fac = self.kl_sched, self.adversary, self.factor_cfg
+        sched, adv, fac, smo = self.kl_sched, self.adversary, self.factor_cfg, self.smooth_cfg
         self.grad_stats = self.ema_stats = self.kl_stats = self.kl_dims = self.adv_stats = self.factor_stats = None
+        self.smooth_stats = None
         # gradient clipping on: the step's norm (optimizer.clip_state[1]) joins running sum / max tensors the same way; a
         # norm that is not finite in float32 (a skipped step, or a huge gradient that was clipped) is counted, not averaged
         if clip:
@@ -487,11 +518,13 @@ class VariationalBaseModelVAE:
             kD = (self.kl_aux.numel() - 4) // 4
             ksum = f64(2 + 2 * kD)
         # likewise the four statistics of the speaker adversary (set_speaker_adversary) and the five of the factor penalty
-        # (set_factor_penalty)
+        # (set_factor_penalty) and of the smoothing penalty (set_smoothing_penalty)
         if adv is not None:
             asum = f64(4)
         if fac is not None:
             fsum = f64(5)
+        if smo is not None:
+            ssum = f64(5)
         for data1, data2, speaker_ids in train_loader:
             data1 = data1.to(self.device, non_blocking=True).float()
             data2 = data2.to(self.device, non_blocking=True).float()
@@ -503,6 +536,8 @@ class VariationalBaseModelVAE:
                 asum.add_(self.adv_out)
             if fac is not None:
                 fsum.add_(self.factor_aux)
+            if smo is not None:
+                ssum.add_(self.smooth_aux)
             if sched is not None:
                 ksum.add_(self.kl_aux[2:4 + 2 * kD])
             if clip:
@@ -519,11 +554,13 @@ class VariationalBaseModelVAE:
             parts["adv"] = asum
         if fac is not None:
             parts["factor"] = fsum
+        if smo is not None:
+            parts["smooth"] = ssum
         if clip:
             parts.update(gsum=gsum, gmax=gmax, clip_counts=opt.clip_state[5:7] - before)
         if ema:
             parts["ema"] = opt.ema_state[1:3]
-        if sched is not None or adv is not None or fac is not None:
+        if sched is not None or adv is not None or fac is not None or smo is not None:
             parts["t"] = opt.dev_state[0:1]
         host = named_to_host(parts)
         tot, n = host["loss"], max(1, steps)
@@ -540,6 +577,12 @@ class VariationalBaseModelVAE:
             self.factor_stats = {"Factor/TC style": f[0] / n, "Factor/TC content": f[1] / n, "Factor/Shared": f[2] / n,
                                  "Factor/MI": f[3] / n, "Factor/Penalty": f[4] / n, "Factor/Weight tc": w[0],
                                  "Factor/Weight shared": w[1]}
+        if smo is not None:
+            f = host["smooth"]
+            w = self.smooth_weights if self.smooth_weights is not None else self.smooth_weights_at(self._step_k)
+            self.smooth_stats = {"Smooth/MS distance dB": f[2] / n, "Smooth/GV ratio dB": f[3] / n, "Smooth/MS loss": f[0] / n,
+                                 "Smooth/GV loss": f[1] / n, "Smooth/Penalty": f[4] / n, "Smooth/Weight ms": w[0],
+                                 "Smooth/Weight gv": w[1]}
         if sched is not None:
             k = host["kl"]
             z1, z2 = [v / n for v in k[2:2 + kD]], [v / n for v in k[2 + kD:2 + 2 * kD]]
@@ -709,6 +752,11 @@ class VariationalBaseModelVAE:
             saved = sd.get("factor_penalty")
             if saved is not None and self.factor_cfg is None and hasattr(self, "set_factor_penalty"):
                 self.set_factor_penalty(saved["tc_weight"], saved["shared_weight"], warmup_steps=saved["warmup_steps"])
+            # ... and the smoothing penalty
+            saved = sd.get("smoothing_penalty")
+            if saved is not None and self.smooth_cfg is None and hasattr(self, "set_smoothing_penalty"):
+                self.set_smoothing_penalty(saved["ms_weight"], saved["gv_weight"], window=saved["window"], floor=saved["floor"],
+                                           warmup_steps=saved["warmup_steps"])
             if sd.get("cuda_rng_state") is not None and torch.device(self.device).type == "cuda":
                 g = torch.cuda.default_generators[torch.device(self.device).index or 0]
                 if self.reducer is not None and self.reducer.rank > 0:
@@ -878,7 +926,7 @@ class VariationalBaseModelVAE:
                    "Loss/Z1 KL Loss": k1 / nb, "Loss/Z2 KL Loss": k2 / nb, "Loss/Z KL Style": ks / nb}
             # what train() left of the opt-in features that are on: gradient clipping, the weight average (FlatAdam.set_grad_clip,
             # set_ema), the speaker adversary, the factor penalty, the KL schedule (set_speaker_adversary, ...)
-            for stats in (self.grad_stats, self.ema_stats, self.adv_stats, self.factor_stats, self.kl_stats):
+            for stats in (self.grad_stats, self.ema_stats, self.adv_stats, self.factor_stats, self.smooth_stats, self.kl_stats):
                 rec.update(stats or {})
             if self.kl_stats and logs_path and self._is_rank0():
                 # beside the logs directory: <log_dir>/kl_dims.json, this epoch's mean KL per latent dimension in nats

@@ -1799,6 +1799,81 @@ class FactorPenaltyFn(torch.autograd.Function):
         return dz, dmu, dlv, None, None, None
 
 
+# ----------------------------------------------------------------------------- smoothing penalty (csrc/msloss.hip)
+MSLOSS_DMIN, MSLOSS_DMAX = 8, 128       # DVAE_MODSPEC_DMIN, DVAE_MODSPEC_DMAX
+_msloss_twiddles: dict = {}
+
+
+def msloss_window(T, D=None) -> int:
+    """The window of the smoothing penalty on trajectories of T frames (default min(64, T)), or ValueError: even, within
+    [MSLOSS_DMIN, MSLOSS_DMAX], a divisor of T."""
+    T = int(T)
+    D = min(64, T) if D is None else int(D)
+    if D % 2 or not MSLOSS_DMIN <= D <= MSLOSS_DMAX or T % D:
+        raise ValueError(f"smoothing penalty: a window of {D} frames on trajectories of {T}: it must be even, lie in "
+                         f"[{MSLOSS_DMIN}, {MSLOSS_DMAX}] and divide {T}")
+    return D
+
+
+def msloss_twiddle(D, dev) -> torch.Tensor:
+    """modspec.twiddle(D) on the device (float64 [D, 2]), one per (device, D), never written again."""
+    key = (_dev_index(dev), int(D))
+    t = _msloss_twiddles.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ops.msloss_twiddle would allocate during a graph capture: run one eager step first")
+        from .modspec import twiddle
+        t = _msloss_twiddles[key] = torch.from_numpy(twiddle(int(D))).to(device=dev, dtype=torch.float64).contiguous()
+    return t
+
+
+class SmoothingPenaltyFn(torch.autograd.Function):
+    """The modulation-spectrum and global-variance loss on the N = 2 Bh reconstructions of a training step (DESIGN.md section
+    4.20): weights[0] L_ms + weights[1] L_gv, a device scalar, from y = rec_hat [N, C, T] and its targets x1, x2 [Bh, C, T]
+    (row n < Bh against x1[n], the others against x2[n - Bh]); windows of D frames, disjoint, no taper.  `weights` (float[2]
+    on the device: w_ms, w_gv with the warm-up applied) and `stats` (float[5]: L_ms, L_gv, msd_db, gv_ratio_db, penalty) belong
+    to the CALLER: a captured graph holds their addresses, the trainer refreshes the one before a step and adds the other up
+    after it.  Two launches forward (dvae_msloss_fwd), one backward (dvae_msloss_bwd: dy, one writer per element); with both
+    device weights 0 the gradient is +0.0 whatever the inputs hold.  The targets get no gradient."""
+
+    @staticmethod
+    def forward(ctx, y, x1, x2, D, floor, weights, stats):
+        y, x1, x2 = y.contiguous(), x1.contiguous(), x2.contiguous()
+        _ok(y, x1, x2, weights, stats)
+        if y.dim() != 3 or x1.dim() != 3 or x1.shape != x2.shape or y.shape[0] != 2 * x1.shape[0] or y.shape[1:] != x1.shape[1:]:
+            raise ValueError("smoothing penalty: y is [2 Bh, C, T], x1 and x2 are [Bh, C, T]")
+        N, C, T = y.shape
+        D, floor = msloss_window(T, D), float(floor)
+        if not floor > 0.0:
+            raise ValueError(f"smoothing penalty: the floor {floor} must be positive")
+        if not (weights.is_contiguous() and weights.numel() >= 2 and stats.is_contiguous() and stats.numel() >= 5):
+            raise ValueError("smoothing penalty: weights is a contiguous float[2], stats a contiguous float[5]")
+        Lib = lib()
+        dev = y.device
+        tw = msloss_twiddle(D, dev)
+        nws = Lib.dvae_msloss_ws_bytes(N, C)
+        if nws < 0:
+            raise ValueError(f"smoothing penalty: {N} rows of {C} bins")
+        ws = torch.empty((nws // 8,), device=dev, dtype=torch.float64)
+        pen = torch.empty((), device=dev, dtype=torch.float32)
+        check(Lib.dvae_msloss_fwd(ptr(y), ptr(x1), ptr(x2), N // 2, C, T, D, floor, ptr(tw), ptr(weights), ptr(stats), ptr(pen),
+                                  ptr(ws), stream()), "dvae_msloss_fwd")
+        ctx.save_for_backward(y, x1, x2, ws, weights, tw)
+        ctx.D, ctx.floor = D, floor
+        return pen
+
+    @staticmethod
+    def backward(ctx, g):
+        y, x1, x2, ws, weights, tw = ctx.saved_tensors
+        g = g.contiguous()
+        _ok(g)
+        N, C, T = y.shape
+        dy = torch.empty_like(y)
+        check(lib().dvae_msloss_bwd(ptr(y), ptr(x1), ptr(x2), N // 2, C, T, ctx.D, ctx.floor, ptr(tw), ptr(weights), ptr(g),
+                                    ptr(ws), ptr(dy), stream()), "dvae_msloss_bwd")
+        return dy, None, None, None, None, None, None
+
+
 def prof_enable(family: int):
     check(lib().dvae_prof_enable(family), "dvae_prof_enable")
 

@@ -131,6 +131,8 @@ class FlatAdam:
         # likewise the factor penalty's configuration (ConvolutionalMulVAE.set_factor_penalty), or None: its warm-up's
         # position is the step count too
         self.factor_penalty = None
+        # ... and the smoothing penalty's (ConvolutionalMulVAE.set_smoothing_penalty)
+        self.smoothing_penalty = None
         # True: the zero_grad ranges of flat_g are known to be zero (the last Adam launch cleared them after reading and no
         # backward kernel has accumulated since: ops._grad_buf resets it) — zero_grad() is then free
         self._clean = False
@@ -440,6 +442,8 @@ class FlatAdam:
             sd["kl_schedule"] = dict(self.kl_schedule)
         if self.factor_penalty is not None:
             sd["factor_penalty"] = dict(self.factor_penalty)
+        if self.smoothing_penalty is not None:
+            sd["smoothing_penalty"] = dict(self.smoothing_penalty)
         return sd
 
     def load_state_dict(self, sd, legacy_layout=None):
@@ -455,6 +459,11 @@ class FlatAdam:
         if saved_fac is not None and self.factor_penalty is not None and dict(saved_fac) != dict(self.factor_penalty):
             raise ValueError(f"optimizer state was trained under the factor penalty {dict(saved_fac)}, this run asks for "
                              f"{dict(self.factor_penalty)}: resume with the same penalty (or with none: the saved one is "
+                             "restored), or start a new run")
+        saved_smo = sd.get("smoothing_penalty")
+        if saved_smo is not None and self.smoothing_penalty is not None and dict(saved_smo) != dict(self.smoothing_penalty):
+            raise ValueError(f"optimizer state was trained under the smoothing penalty {dict(saved_smo)}, this run asks for "
+                             f"{dict(self.smoothing_penalty)}: resume with the same penalty (or with none: the saved one is "
                              "restored), or start a new run")
         fmt = int(sd.get("format", 1))
         if fmt == 1:

@@ -24,6 +24,11 @@ reaches the encoder reversed and scaled by F (ConvolutionalMulVAE.set_speaker_ad
 training step, inside the replayed step (ConvolutionalMulVAE.set_factor_penalty, csrc/factor.hip): F times the total correlation
 inside the style and inside the content block, --shared-weight times the information the two blocks share; --tc-weight 0 alone
 only monitors; Factor/... in scalars.jsonl; the configuration rides in the .opt sidecar and a resume continues it.
+--ms-loss-weight F [--gv-loss-weight F] [--ms-loss-window D] [--ms-loss-floor F] [--ms-loss-warmup-steps N] (new, opt-in): the
+modulation-spectrum and global-variance loss on rec_hat of every training step, inside the replayed step
+(ConvolutionalMulVAE.set_smoothing_penalty, csrc/msloss.hip): F times the mean squared distance between the log modulation spectra
+of the reconstruction and of its input, --gv-loss-weight times that between their log global variances; --ms-loss-weight 0 alone
+only monitors; Smooth/... in scalars.jsonl; the configuration rides in the .opt sidecar and a resume continues it.
 --convert (reference variational_base_vae.py:243-330, minus plots): the first --convert-count sorted utterances of
 --src_spk, each with a random utterance of --trg_spk (seeded by --seed), through `convert_mel`; the converted mels are
 voiced by the GPU Griffin-Lim inverse of the mel front-end (frontend.MelInverter, --griffin-lim-iters) instead of the
@@ -145,9 +150,24 @@ def get_parse():
                         "--tc-weight 0")
     p.add_argument("--factor-warmup-steps", type=int, default=0,
                    help="--tc-weight / --shared-weight: both weights rise linearly from 0 over this many optimiser steps")
+    p.add_argument("--ms-loss-weight", type=float, default=None,
+                   help="penalise the mean squared distance between the log modulation spectra of rec_hat and of the input it "
+                        "reconstructs on every training step, with this weight, in nats^2 (0 without --gv-loss-weight: the "
+                        "statistics are computed, the model is untouched: a monitor).  Default: off")
+    p.add_argument("--gv-loss-weight", type=float, default=None,
+                   help="penalise the mean squared distance between their log global variances, with this weight; alone it "
+                        "implies --ms-loss-weight 0")
+    p.add_argument("--ms-loss-window", type=int, default=None,
+                   help="--ms-loss-weight: frames of a window (even, 8 .. 128, a divisor of --samples_length; default min(64, T))")
+    p.add_argument("--ms-loss-floor", type=float, default=0.003,
+                   help="--ms-loss-weight / --gv-loss-weight: the ripple under which a logarithm stops following its argument "
+                        "(0.003 = 0.3 dB of the normalised range; a setting, not a measured optimum)")
+    p.add_argument("--ms-loss-warmup-steps", type=int, default=0,
+                   help="--ms-loss-weight / --gv-loss-weight: both weights rise linearly from 0 over this many optimiser steps")
     return p
 
 
+SMOOTH_KEYS = ("ms_loss_weight", "gv_loss_weight", "ms_loss_window", "ms_loss_floor", "ms_loss_warmup_steps")
 FACTOR_KEYS = ("tc_weight", "shared_weight", "factor_warmup_steps")
 ADV_KEYS = ("adv_weight", "adv_hidden", "adv_lr", "adv_warmup_steps")
 KL_KEYS = ("kl_schedule", "kl_start", "kl_warmup_steps", "kl_cycles", "kl_ratio", "free_bits", "free_bits_style",
@@ -440,6 +460,9 @@ def main(argv=None):
         if all(cfg[k] == get_parse().get_default(k) for k in FACTOR_KEYS):
             for k in FACTOR_KEYS:   # likewise the flags of the factor penalty
                 del cfg[k]
+        if all(cfg[k] == get_parse().get_default(k) for k in SMOOTH_KEYS):
+            for k in SMOOTH_KEYS:   # ... and of the smoothing penalty
+                del cfg[k]
         with open(os.path.join(args.log_dir, "config.json"), "w") as fp:
             json.dump(cfg, fp, indent=4)
     vsc = ConvolutionalMulVAE(args.dataset, args.samples_length, 80, args.latent_size, args.lr, args.alpha,
@@ -470,6 +493,21 @@ def main(argv=None):
                                    warmup_steps=args.factor_warmup_steps)
         except ValueError as e:
             raise SystemExit(f"--tc-weight / --shared-weight: {e}")
+    smooth_on = args.ms_loss_weight is not None or args.gv_loss_weight is not None
+    if not smooth_on and any(getattr(args, k) != get_parse().get_default(k) for k in SMOOTH_KEYS[2:]):
+        raise SystemExit("--ms-loss-window / --ms-loss-floor / --ms-loss-warmup-steps configure --ms-loss-weight / "
+                         "--gv-loss-weight: give one of them too (a resume without any of the five restores the saved "
+                         "configuration)")
+    if smooth_on:
+        if not args.train:
+            raise SystemExit("--ms-loss-weight / --gv-loss-weight: the smoothing penalty belongs to training (--train true)")
+        try:
+            vsc.set_smoothing_penalty(args.ms_loss_weight if args.ms_loss_weight is not None else 0.0,
+                                      args.gv_loss_weight if args.gv_loss_weight is not None else 0.0,
+                                      window=args.ms_loss_window, floor=args.ms_loss_floor,
+                                      warmup_steps=args.ms_loss_warmup_steps)
+        except ValueError as e:
+            raise SystemExit(f"--ms-loss-weight / --gv-loss-weight: {e}")
     dp = world > 1 or os.environ.get("DVAE_FORCE_DDP", "0") == "1"
     if dp:
         setup_data_parallel(vsc, args.seed)

@@ -50,7 +50,8 @@ extern "C" {
  * dvae_loss_bwd_sched, dvae_loss_sched_t, DVAE_LOSS_MAX_D): additive, and the suites of the two earlier additions pin 319.
  * Likewise the latent map's four entry points (dvae_tsne_nn, dvae_tsne_affinities, dvae_tsne_forces, dvae_tsne_update) and
  * the speaker adversary's two (dvae_adv_rows, dvae_adv_params), and the factor penalty's three (dvae_factor_ws_bytes,
- * dvae_factor_fwd, dvae_factor_bwd). */
+ * dvae_factor_fwd, dvae_factor_bwd), and the modulation-spectrum loss's three (dvae_msloss_ws_bytes, dvae_msloss_fwd,
+ * dvae_msloss_bwd). */
 #define DVAE_ABI_VERSION 319
 int dvae_version(void);
 
@@ -619,6 +620,42 @@ int dvae_modspec_group_sum(const float* rows, const int* order, int norder, cons
 int dvae_modspec_filter(const float* windows, int nwin, int C, int D, const double* twiddle, const double* mu_n,
                         const double* sigma_n, const double* mu_g, const double* sigma_g, double alpha, double max_gain_db,
                         float* out, void* stream);
+
+/* ---- modulation-spectrum and global-variance loss of the train step (ops.SmoothingPenaltyFn) ----
+ * The reference's loss_functionGVAE2 (disentangled_vae.py:310-327) is L1 plus KL; this ADDS the squared distance between the log
+ * modulation spectra, and between the log global variances, of the reconstruction and of its own target (modulation-spectrum-
+ * constrained training, Takamichi et al., in the form an autoencoder allows), forward and backward.  Added at 319 without a new
+ * revision: purely additive.
+ * y [N, C, T] fp32 dense, N = 2 Bh; its target x: row n < Bh is x1[n], otherwise x2[n - Bh], both [Bh, C, T] fp32 dense.  The
+ * W = T / D windows of a row are disjoint, no taper.  floor > 0; eps_ms = D floor^2, eps_gv = floor^2.  twiddle: as above.
+ *   per (row, window, bin): d_t = y_t - mean_t(y), Y_k = sum_t d_t e^{-2 pi i k t / D} for k = 1 .. H = D/2 (float64, t in index
+ *     order, the twiddle at k t mod D), P_k = |Y_k|^2, s_k = ln(P_k + eps_ms), Delta_k = s_k - s^x_k
+ *     L_ms = the mean of Delta^2 over all M = N W C H elements
+ *   per (row, bin): m = the mean over the row's T frames, v = (1 / T) sum_t (y_t - m)^2, g = ln(v + eps_gv)
+ *     L_gv = the mean of (g - g^x)^2 over N C
+ * dvae_msloss_fwd (two launches) writes stats [5] = {L_ms, L_gv, msd_db = (10 / ln 10) sqrt(L_ms), gv_ratio_db = (10 / ln 10)
+ *   mean(g - g^x), penalty = weights[0] L_ms + weights[1] L_gv}, each float64 rounded once.  weights: DEVICE pointer to
+ *   {w_ms, w_gv}.  penalty (may be null): one more float that receives stats[4].  ws (dvae_msloss_ws_bytes(N, C) bytes, 8-byte
+ *   aligned) receives three float64 partial sums per workgroup (row n, tile of 16 bins: index n ceil(C / 16) + tile) and per
+ *   (row, bin) m and 2 (g - g^x) / (v + eps_gv) for dvae_msloss_bwd.  Orders: a workgroup's 256 threads add their (bin, k)
+ *   items window by window and then go through a binary tree; m and v: lane j of 16 the frames j, j + 16, ..., then the xor
+ *   tree 8 .. 1; the second launch: thread r of 256 the workgroups r, r + 256, ... from +0, then a binary tree.
+ * dvae_msloss_bwd (one launch, the same grid) reads y, x1, x2 and ws as dvae_msloss_fwd left it and stores
+ *     dy_t = gscale (w_ms dL_ms/dy_t + w_gv dL_gv/dy_t), float64 rounded once to fp32, one writer per element, with
+ *     dL_ms/dd_t = (4 / M) sum_k Delta_k / (P_k + eps_ms) (Re Y_k cos th_kt - Im Y_k sin th_kt), th_kt = 2 pi k t / D, k in index
+ *     order; dL_ms/dy_t = that minus its mean over the window;  dL_gv/dy_t = (1 / (N C)) 2 (g - g^x) / (v + eps_gv) (2 / T) (y_t - m)
+ *   gscale: DEVICE pointer to the incoming gradient of the penalty; null: 1.  A zero result is stored as +0.0.  When the device
+ *   values of both weights are exactly 0, dy is +0.0 everywhere whatever y and x hold: the feature only monitors.
+ * No atomics; every order is a function of (C, T, D) alone: a row's dy depends on the other rows through M and N only, and two
+ * launches give the same bits.  Null pointers (penalty and gscale aside), Bh < 1, C < 1, C > 65535, an odd or out-of-range D,
+ * T % D != 0, !(floor > 0) (or a floor whose square is not: eps_gv must be positive), a twiddle or ws that is not 8-byte
+ * aligned return DVAE_EINVAL and launch nothing (dvae_msloss_ws_bytes: -1 for N < 1 or such a C). */
+int64_t dvae_msloss_ws_bytes(int N, int C);
+int dvae_msloss_fwd(const float* y, const float* x1, const float* x2, int Bh, int C, int T, int D, double floor,
+                    const double* twiddle, const float* weights, float* stats, float* penalty, void* ws, void* stream);
+int dvae_msloss_bwd(const float* y, const float* x1, const float* x2, int Bh, int C, int T, int D, double floor,
+                    const double* twiddle, const float* weights, const float* gscale, const void* ws, float* dy,
+                    void* stream);
 
 /* ---- mel front-end: preprocessing/utils.py:68-73 `melspectrogram` = lws STFT (1024/256, "speech" window)
  * -> |.| -> 80-mel projection (librosa.filters.mel) -> dB (:127-129) - ref_level_db -> normalise to [0,1] (:136-137).
