@@ -550,31 +550,22 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         epochs under one fixed objective.  Data parallel: every rank computes the same weight from the same step count;
         free bits gate on each rank's LOCAL minibatch; nothing is exchanged."""
         from ..kl_schedule import KLSchedule, expand_free_bits
-        opt = self.optimizer
         if kind is None:
             if free_bits is not None:
                 raise ValueError("set_kl_schedule: free_bits needs a schedule (\"constant\" keeps the weight at kl_cof)")
-            self.kl_sched = None
-            opt.kl_schedule = None
+            self._feature("kl", None).sched = None
             return
         S, Cn = self.model.speaker_size, self.model.latent_dim - self.model.speaker_size
         D = S + Cn
         sched = KLSchedule(kind, start, steps, cycles, ratio, expand_free_bits(free_bits, S, Cn))
-        dev = opt.flat_p.device
-        if dev.type != "cuda":
-            raise RuntimeError("set_kl_schedule: the scheduled loss runs only on the HIP device (no CPU fallback)")
         if D > _lib.LOSS_MAX_D:
             raise ValueError(f"set_kl_schedule: {D} latent dimensions, the loss kernels take {_lib.LOSS_MAX_D}")
-        if self._kl_coef is None:       # allocated once: a captured graph holds their addresses
-            self._kl_coef = torch.zeros(8, device=dev, dtype=torch.float32)
-            self.kl_aux = torch.zeros(4 + 4 * D, device=dev, dtype=torch.float32)
-            self._kl_fb = torch.zeros(D, device=dev, dtype=torch.float32)
+        f = self._feature("kl", sched.params(), "set_kl_schedule: the scheduled loss", 8, 4 + 4 * D)
+        if f.fb is None:                # allocated once, like the other two
+            f.fb = torch.zeros(D, device=f.coef.device, dtype=torch.float32)
         if sched.free_bits is not None:
-            self._kl_fb.copy_(torch.tensor(sched.free_bits, dtype=torch.float32))
-        self.kl_sched = sched
-        opt.kl_schedule = sched.params()        # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
-        self._feature_set("kl")
-        self.kl_weight = None
+            f.fb.copy_(torch.tensor(sched.free_bits, dtype=torch.float32))
+        f.sched = sched
 
     def set_speaker_adversary(self, weight=None, *, n_speakers=None, hidden=256, lr=1e-3, warmup_steps=0, seed=0):
         """A speaker classifier on the content means of every TRAINING step, trained inside the replayed graph, whose
@@ -587,8 +578,9 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         compared under one fixed objective.  `step` / `step_async` then need `speaker_ids`.  `train()` reports Adv/CE,
         Adv/Accuracy (of the classifier on the training batches, while it learns) and Adv/Weight in `adv_stats`.
         Not data parallel: with a reducer attached this raises, and attach_reducer raises while it is on."""
+        f = self.features["adv"]
         if weight is None:
-            self.adversary, self.adv_config = None, None
+            self._feature("adv", None).net = None
             return
         from ..adversary import SpeakerAdversary
         weight, warmup_steps = float(weight), int(warmup_steps)
@@ -598,21 +590,15 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
             raise ValueError("set_speaker_adversary: n_speakers (the number of speakers of the corpus) is required")
         if self.reducer is not None:
             raise ValueError("set_speaker_adversary: the adversary is not trained data parallel (a reducer is attached)")
-        dev = self.optimizer.flat_p.device
-        if dev.type != "cuda":
-            raise RuntimeError("set_speaker_adversary: the adversary runs only on the HIP device (no CPU fallback)")
+        dev = self._hip_device("set_speaker_adversary: the adversary")
         Cn = self.model.latent_dim - self.model.speaker_size
         cfg = dict(weight=weight, n_speakers=int(n_speakers), hidden=int(hidden), lr=float(lr), warmup_steps=warmup_steps,
                    seed=int(seed))
-        same_net = self.adversary is not None and \
-            all(self.adv_config[k] == cfg[k] for k in ("n_speakers", "hidden", "lr", "seed"))
+        same_net = f.on and all(f.cfg[k] == cfg[k] for k in ("n_speakers", "hidden", "lr", "seed"))
         if not same_net:        # a new classifier; only the weight or its warm-up changed: the one that is learning stays
-            self.adversary = SpeakerAdversary(Cn, n_speakers, hidden=hidden, seed=seed, device=dev, lr=lr)
-        if self._adv_coef is None:      # allocated once: a captured graph holds its address
-            self._adv_coef = torch.zeros(1, device=dev, dtype=torch.float32)
-        self.adv_config = cfg
-        self._feature_set("adv")
-        self.adv_weight = self.adv_out = self.adv_pred = self.adv_stats = None
+            f.net = SpeakerAdversary(Cn, n_speakers, hidden=hidden, seed=seed, device=dev, lr=lr)
+        self._feature("adv", cfg, "set_speaker_adversary: the adversary", 1)
+        f.aux = f.pred = None
 
     def set_factor_penalty(self, tc_weight=None, shared_weight=0.0, *, warmup_steps=0):
         """The beta-TCVAE penalty (Chen et al. 2018) on the minibatch of every TRAINING step, inside the replayed graph
@@ -627,11 +613,8 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         `Val/Loss` and checkpoints/best.json do not see the penalty: epochs stay compared under one fixed objective.
         Data parallel: every rank penalises its LOCAL rows and computes the same weights from the same step count; nothing is
         exchanged (not run on more than one GPU)."""
-        opt = self.optimizer
         if tc_weight is None:
-            self.factor_cfg = None
-            self.model.factor_tap = False
-            opt.factor_penalty = None
+            self._feature("factor", None)
             return
         try:
             tc_weight, shared_weight, warmup_steps = float(tc_weight), float(shared_weight), int(warmup_steps)
@@ -647,17 +630,8 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         if 2 * int(self.batch_size) > _lib.FACTOR_MAX_N:
             raise ValueError(f"set_factor_penalty: {2 * int(self.batch_size)} rows per step, the penalty's kernels take "
                              f"{_lib.FACTOR_MAX_N}")
-        dev = opt.flat_p.device
-        if dev.type != "cuda":
-            raise RuntimeError("set_factor_penalty: the penalty runs only on the HIP device (no CPU fallback)")
-        if self._fac_coef is None:      # allocated once: a captured graph holds their addresses
-            self._fac_coef = torch.zeros(2, device=dev, dtype=torch.float32)
-            self.factor_aux = torch.zeros(5, device=dev, dtype=torch.float32)
-        self.factor_cfg = dict(tc_weight=tc_weight, shared_weight=shared_weight, warmup_steps=warmup_steps)
-        self.model.factor_tap = True
-        opt.factor_penalty = dict(self.factor_cfg)      # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
-        self._feature_set("factor")
-        self.factor_weights = self.factor_stats = None
+        self._feature("factor", dict(tc_weight=tc_weight, shared_weight=shared_weight, warmup_steps=warmup_steps),
+                         "set_factor_penalty: the penalty", 2, 5)
 
     def set_smoothing_penalty(self, ms_weight=None, gv_weight=0.0, *, window=None, floor=0.003, warmup_steps=0):
         """The modulation-spectrum and global-variance loss on rec_hat of every TRAINING step, inside the replayed graph
@@ -673,11 +647,8 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
         means as Smooth/... in `smooth_stats`.  Validation, `Val/Loss` and checkpoints/best.json do not see the penalty.
         Data parallel: every rank penalises its LOCAL rows with the same weights; nothing is exchanged (not run on more than
         one GPU)."""
-        opt = self.optimizer
         if ms_weight is None:
-            self.smooth_cfg = None
-            self.model.smooth_tap = False
-            opt.smoothing_penalty = None
+            self._feature("smooth", None)
             return
         try:
             ms_weight, gv_weight, floor, warmup_steps = float(ms_weight), float(gv_weight), float(floor), int(warmup_steps)
@@ -692,34 +663,48 @@ class ConvolutionalMulVAE(VariationalBaseModelVAE):
             raise ValueError(f"set_smoothing_penalty: the floor {floor} must be positive and finite")
         from .. import ops
         window = ops.msloss_window(self.model.n_frames, window)      # ValueError: odd, out of range, no divisor of T
-        dev = opt.flat_p.device
+        f = self._feature("smooth", dict(ms_weight=ms_weight, gv_weight=gv_weight, window=window, floor=floor,
+                                            warmup_steps=warmup_steps), "set_smoothing_penalty: the penalty", 2, 5)
+        ops.msloss_twiddle(window, f.coef.device)   # the device table of this window: allocated here, outside any capture
+
+    def _hip_device(self, who):
+        dev = self.optimizer.flat_p.device
         if dev.type != "cuda":
-            raise RuntimeError("set_smoothing_penalty: the penalty runs only on the HIP device (no CPU fallback)")
-        if self._smooth_coef is None:   # allocated once: a captured graph holds their addresses
-            self._smooth_coef = torch.zeros(2, device=dev, dtype=torch.float32)
-            self.smooth_aux = torch.zeros(5, device=dev, dtype=torch.float32)
-        ops.msloss_twiddle(window, dev)     # the device table of this window: allocated here, outside any capture
-        self.smooth_cfg = dict(ms_weight=ms_weight, gv_weight=gv_weight, window=window, floor=floor, warmup_steps=warmup_steps)
-        self.model.smooth_tap = True
-        opt.smoothing_penalty = dict(self.smooth_cfg)   # rides in the optimiser's state_dict: the .opt sidecar of a checkpoint
-        self._feature_set("smooth")
-        self.smooth_weights = self.smooth_stats = None
+            raise RuntimeError(f"{who} runs only on the HIP device (no CPU fallback)")
+        return dev
+
+    def _feature(self, name, cfg, who=None, n_coef=0, n_aux=0):
+        """The common tail of the setters, after their validation: the feature `name` of the table (step_features.py) gets the
+        configuration `cfg` (None: off) and its device buffers, the model leaves the inputs the feature taps, and the
+        configuration rides in the optimiser's state_dict (the .opt sidecar): a warm-up's position IS the step count `t`."""
+        f, kept = self.features[name], self.optimizer.step_features
+        if cfg is not None:
+            dev = self._hip_device(who)
+            if f.coef is None:          # allocated once: a captured graph holds their addresses
+                f.coef = torch.zeros(n_coef, device=dev, dtype=torch.float32)
+                f.aux = torch.zeros(n_aux, device=dev, dtype=torch.float32) if n_aux else None
+            self._feature_set(name)
+        f.cfg = cfg
+        if f.tap:
+            setattr(self.model, f.tap, cfg is not None)
+        kept.pop(f.key, None)
+        if f.key and cfg is not None:
+            kept[f.key] = dict(cfg)
+        return f
 
     def kl_weight_at(self, k, epoch=1):
         """The KL weight of the step that runs after `k` optimiser steps, in epoch `epoch` (kl_schedule.KLSchedule)."""
-        if self.kl_sched is None:
-            return float(self.kl_cof)
-        return self.kl_sched.weight_at(k, epoch, self.kl_cof)
+        f = self.features["kl"]
+        return f.weights_at(k, epoch)[1] if f.on else float(self.kl_cof)
 
     def losses_vector_full(self, x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv):
         """losses_vector on the unsplit outputs of `DisentangledVAE.forward_full` (the training step's path).  While a KL
         schedule is on (set_kl_schedule) the weights come from the device and `self.kl_aux` receives the per-dimension KL."""
         inv_b = 1.0 / float(self.batch_size)
-        sched = self.kl_sched
-        if sched is not None:
+        f = self.features["kl"]
+        if f.on:
             return ops.LossGVAE2SchedFn.apply(x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv, inv_b, -0.5 / x1.shape[0], -inv_b,
-                                              self._kl_coef, self._kl_fb if sched.free_bits is not None else None,
-                                              q_mu.shape[1], self.kl_aux)
+                                              f.coef, f.fb if f.sched.free_bits is not None else None, q_mu.shape[1], f.aux)
         return ops.LossGVAE2FullFn.apply(x1, x2, rec, rec_hat, q_mu, q_lv, s_mu, s_lv, inv_b, -0.5 / x1.shape[0], -inv_b,
                                          self.mse_cof, self.kl_cof)
 

@@ -23,6 +23,7 @@ from pathlib import Path
 import torch
 
 from ..optim import ScalarSender
+from ..step_features import FEATURES
 
 
 def named_to_host(parts):
@@ -70,18 +71,12 @@ class VariationalBaseModelVAE:
         self._graph = None
         self._graph_sig = None
         self._graph_calls = 0
-        # the opt-in features of the train step (the subclass's set_kl_schedule / set_speaker_adversary / set_factor_penalty /
-        # set_smoothing_penalty):
-        # None is "off".  Their weights at optimiser step k are device scalars, sent before the step by _sync_step_coefs
-        self.kl_sched = self.adversary = self.adv_config = self.factor_cfg = self.smooth_cfg = None
-        self.kl_weight = self.adv_weight = self.factor_weights = self.smooth_weights = None      # as last computed for a step
-        self.kl_stats = self.kl_dims = self.adv_stats = self.factor_stats = self.grad_stats = self.ema_stats = None
-        self.smooth_stats = None
-        self.adv_out = self.adv_pred = None
+        # the opt-in features of the train step (step_features.py) by name, in the order of their backward roots: each holds its
+        # configuration (None is "off"; the subclass's setters switch it), its device buffers and its epoch record
+        self.features = {cls.name: cls(self) for cls in FEATURES}
+        self.grad_stats = self.ema_stats = None
         self._step_k = None         # the host's count of optimizer.t (None: read it before the next step)
-        self._kl_epoch = 1
-        self._kl_coef = self._adv_coef = self._fac_coef = self._smooth_coef = None      # the device scalars: allocated once, by the setters
-        self._coef_sent = {}        # feature -> the weights its device scalars hold
+        self._epoch = 1             # the epoch train() is in (a schedule may look at it)
         self._sender = ScalarSender()
         self._loss_seed = None
         self._fold_before_shard = None
@@ -140,97 +135,72 @@ class VariationalBaseModelVAE:
     def _graph_signature(self, data1):
         from .. import ops
         opt = self.optimizer
-        # with a KL schedule the two weights are read from the device (set_kl_schedule): their values are no part of the graph
-        kl = self._kl_signature()
-        cofs = () if kl else (float(self.mse_cof), float(self.kl_cof))
+        on = self._features_on(ranked=True)
+        # a feature whose kernels read the two loss weights from the device (a KL schedule): their values are no part of the graph
+        cofs = () if any(f.device_cofs for f in on) else (float(self.mse_cof), float(self.kl_cof))
         return (tuple(data1.shape), tuple(opt.betas), float(opt.eps)) + cofs + (
                 int(self.batch_size), bool(self.model.training),
                 self.reducer is not None, getattr(self.reducer, "world_size", 1), ops.current_mode(),
-                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature() + kl + self._adv_signature() \
-            + self._factor_signature() + self._smooth_signature()
+                bool(ops.LSTM_PERSISTENT), bool(ops.deterministic())) + self._clip_signature() + self._ema_signature() \
+            + sum((f.signature() for f in on), ())
 
-    def _adv_signature(self):
-        """The speaker adversary on/off and its shape change the launches of a step; its weight does not (a device scalar,
-        _sync_step_coefs).  Nothing is added while it is off."""
-        adv = self.adversary
-        return (("adv", adv.hidden, adv.n_speakers),) if adv is not None else ()
+    def _features_on(self, ranked=False):
+        """The features that are on, in the table's order; `ranked`: in that of the graph signature and of the step's send."""
+        on = [f for f in self.features.values() if f.on]
+        return sorted(on, key=lambda f: f.rank) if ranked else on
 
-    def _factor_signature(self):
-        """The factor penalty on/off changes the launches of a step; its two weights and their warm-up do not (device scalars,
-        _sync_step_coefs).  Nothing is added while it is off."""
-        return (("factor",),) if self.factor_cfg is not None else ()
+    # the features' state under the names the setters' docstrings, DESIGN.md, the scripts and the suites use
+    _of = lambda name, *attrs: [property(lambda self, a=a: getattr(self.features[name], a)) for a in attrs]     # noqa: E731
+    kl_sched, kl_aux, kl_stats, kl_dims, _kl_coef = _of("kl", "sched", "aux", "report", "dims", "coef")
+    adversary, adv_config, adv_out, adv_pred, adv_stats, _adv_coef = _of("adv", "net", "cfg", "aux", "pred", "report", "coef")
+    factor_cfg, factor_aux, factor_stats, _fac_coef, factor_weights = _of("factor", "cfg", "aux", "report", "coef", "weights")
+    smooth_cfg, smooth_aux, smooth_stats, _smooth_coef, smooth_weights = _of("smooth", "cfg", "aux", "report", "coef", "weights")
+    kl_weight = property(lambda self: (self.features["kl"].weights or (None, None))[1])     # of (mse_cof, KL weight)
+    adv_weight = property(lambda self: (self.features["adv"].weights or (None,))[0])
+    del _of
 
-    def _smooth_signature(self):
-        """The smoothing penalty on/off, its window and its floor change the launches of a step (both are kernel arguments); its
-        two weights and their warm-up do not (device scalars, _sync_step_coefs).  Nothing is added while it is off."""
-        cfg = self.smooth_cfg
-        return (("smooth", cfg["window"], cfg["floor"]),) if cfg is not None else ()
+    # the weights of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps) (step_features.ramp)
+    smooth_weights_at = lambda self, k: self.features["smooth"].weights_at(k)       # noqa: E731  (w_ms, w_gv)
+    factor_weights_at = lambda self, k: self.features["factor"].weights_at(k)       # noqa: E731  (w_tc, w_sh)
+    adv_weight_at = lambda self, k: self.features["adv"].weights_at(k)[0]           # noqa: E731  the reversal weight
 
-    def smooth_weights_at(self, k):
-        """(w_ms, w_gv) of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
-        cfg = self.smooth_cfg
-        n = int(cfg["warmup_steps"])
-        f = 1.0 if n <= 0 else min(1.0, k / n)
-        return float(cfg["ms_weight"]) * f, float(cfg["gv_weight"]) * f
-
-    def factor_weights_at(self, k):
-        """(w_tc, w_sh) of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
-        cfg = self.factor_cfg
-        n = int(cfg["warmup_steps"])
-        f = 1.0 if n <= 0 else min(1.0, k / n)
-        return float(cfg["tc_weight"]) * f, float(cfg["shared_weight"]) * f
-
-    def adv_weight_at(self, k):
-        """The reversal weight of the step that runs after `k` optimiser steps: weight min(1, k / warmup_steps)."""
-        cfg = self.adv_config
-        w, n = float(cfg["weight"]), int(cfg["warmup_steps"])
-        return w if n <= 0 else w * min(1.0, k / n)
-
-    def _feature_set(self, feature):
-        """A setter switched `feature` ("kl", "adv", "factor", "smooth") on or reconfigured it: its device scalars are sent afresh, and
-        every feature takes the optimiser's true step count at the next step (one read of FlatAdam.t)."""
-        self._coef_sent.pop(feature, None)
+    def _feature_set(self, name):
+        """A setter switched the feature `name` of the table on or reconfigured it: its device scalars are sent afresh, what it
+        last computed and reported is forgotten, and every feature takes the optimiser's true step count at the next step (one
+        read of FlatAdam.t)."""
+        f = self.features[name]
+        f.weights = f.sent = f.report = None
         self._step_k = None
 
     def _sync_step_coefs(self):
-        """Host -> device copy of the weights of the step about to run, for every feature that is on and whose weights changed
-        since its last copy: (mse_cof, KL weight) of a schedule, the adversary's reversal weight, the pair of either penalty.  Beside
-        optimizer.sync_scalars, never inside a capture.  The step about to run is number `_step_k` by the host's ONE count,
-        which starts from FlatAdam.t (one read) and is set right from it wherever the host reads the device anyway."""
-        if self.kl_sched is None and self.adversary is None and self.factor_cfg is None and self.smooth_cfg is None:
+        """Host -> device copy of the weights of the step about to run (StepFeature.weights_at), for every feature that is on
+        and whose weights changed since its last copy, in ONE send.  Beside optimizer.sync_scalars, never inside a capture.
+        The step about to run is number `_step_k` by the host's ONE count, which starts from FlatAdam.t (one read) and is set
+        right from it wherever the host reads the device anyway."""
+        on = self._features_on(ranked=True)
+        if not on:
             return              # the plain trainer: no read of optimizer.t (a device-to-host sync), no count
         if self._step_k is None:
             self._step_k = self.optimizer.t
-        k, want = self._step_k, {}
-        if self.kl_sched is not None:
-            self.kl_weight = float(self.kl_weight_at(k, self._kl_epoch))
-            want["kl"] = (self._kl_coef, (float(self.mse_cof), self.kl_weight))
-        if self.adversary is not None:
-            self.adv_weight = float(self.adv_weight_at(k))
-            want["adv"] = (self._adv_coef, (self.adv_weight,))
-        if self.factor_cfg is not None:
-            self.factor_weights = self.factor_weights_at(k)
-            want["factor"] = (self._fac_coef, self.factor_weights)
-        if self.smooth_cfg is not None:
-            self.smooth_weights = self.smooth_weights_at(k)
-            want["smooth"] = (self._smooth_coef, self.smooth_weights)
-        send = {f: bv for f, bv in want.items() if self._coef_sent.get(f) != bv[1]}
+        for f in on:
+            f.weights = f.weights_at(self._step_k, self._epoch)
+        send = [f for f in on if f.sent != f.weights]
         if send:
             # through the ring of pinned slots (optim.ScalarSender): a per-step schedule must not stall the host
-            self._sender.send([(buf[:len(vals)], vals) for buf, vals in send.values()])
-            self._coef_sent.update((f, vals) for f, (_, vals) in send.items())
+            self._sender.send([(f.coef[:len(f.weights)], f.weights) for f in send])
+            for f in send:
+                f.sent = f.weights
         self._step_k += 1       # Adam advances t with this step (or skips it: set right at the next read of t)
 
     def _prepare_step(self, dev):
         """Everything of the host's that has to happen before a step and never inside a capture, in one place: _step_graph
         calls it before capture / replay, the eager step when _step_graph has not."""
-        adv = self.adversary
-        if adv is not None:
-            self._sync_adv_guard()              # may allocate the buffers of the adversary's non-finite guard
-            adv.optimizer.sync_scalars(1.0)     # after the first step nothing: its step() sends the same value
-        if adv is not None or self.factor_cfg is not None or self.smooth_cfg is not None:
+        on = self._features_on()
+        for f in on:
+            f.before_step()                     # may allocate (the buffers of the adversary's non-finite guard)
+        if any(f.rooted for f in on):
             from .. import ops
-            ops.unit_seed(dev)                  # allocated outside the capture
+            ops.unit_seed(dev)                  # the seed of the extra roots: allocated outside the capture
         self._sync_step_coefs()
 
     def _adv_labels(self, speaker_ids, out=None):
@@ -246,12 +216,6 @@ class VariationalBaseModelVAE:
         out[:ids.numel()].copy_(ids)
         out[ids.numel():].copy_(ids)
         return out
-
-    def _kl_signature(self):
-        """A KL schedule on/off, and free bits on/off, change the loss launches of a step; the weight does not (a device
-        scalar, _sync_step_coefs).  Nothing is added while it is off."""
-        sched = self.kl_sched
-        return (("kl_sched", sched.free_bits is not None),) if sched is not None else ()
 
     def _clip_signature(self):
         """Gradient clipping on/off and the guard change the launches of a step; the VALUE of max_norm does not (a device
@@ -279,33 +243,12 @@ class VariationalBaseModelVAE:
             self._prepare_step(data1.device)
         return self._train_step_body(data1, data2, labels2)
 
-    def _sync_adv_guard(self):
-        """The guard of the model's optimiser covers the adversary's: a step the one skips on a non-finite gradient must not
-        feed NaNs into the other's moments.  The first set_grad_clip allocates: like every other host-side refresh this runs
-        before the step, never inside a capture (the model's guard is part of the graph signature, so switching it captures
-        again, after this)."""
-        adv = self.adversary
-        guard = getattr(self.optimizer, "max_norm", None) is not None
-        if guard != (adv.optimizer.max_norm is not None):
-            adv.optimizer.set_grad_clip(float("inf") if guard else None, skip_nonfinite=True)
-
     def _train_step_body(self, data1, data2, labels2=None):
         self.optimizer.zero_grad()
-        adv, fac, smo = self.adversary, self.factor_cfg, self.smooth_cfg
+        rooted = [f for f in self._features_on() if f.rooted]
         unsplit = hasattr(self, "losses_vector_full") and hasattr(self.model, "forward_full")
-        outs = None
-        if adv is not None:
-            if labels2 is None:
-                raise ValueError("the speaker adversary is on (set_speaker_adversary): the step needs speaker_ids")
-            if not unsplit:
-                raise RuntimeError("the speaker adversary needs the unsplit forward (forward_full / losses_vector_full)")
-            if self.reducer is not None:
-                raise ValueError("the speaker adversary is not trained data parallel")
-            adv.optimizer.zero_grad()       # store-first parameters only: no launch, the written-once counts start over
-        if fac is not None and not unsplit:
-            raise RuntimeError("the factor penalty needs the unsplit forward (forward_full / losses_vector_full)")
-        if smo is not None and not unsplit:
-            raise RuntimeError("the smoothing penalty needs the unsplit forward (forward_full / losses_vector_full)")
+        for f in rooted:
+            f.require(unsplit, labels2)     # raises before anything is launched
         if unsplit:
             # the eight scalars as one vector (fused loss kernels) on the UNSPLIT outputs; backward is seeded with the
             # constant (1, 0, ..., 0): `vec[0].backward()` and the reference's ten output slices cost ~25 zero-fill /
@@ -322,37 +265,11 @@ class VariationalBaseModelVAE:
             if self._loss_seed is None or self._loss_seed.device != vec.device:
                 self._loss_seed = torch.zeros(8, device=vec.device)
                 self._loss_seed[0] = 1.0
-            roots, seeds = [vec], [self._loss_seed]
-            if fac is not None:
-                # LOSS + penalty: the penalty reads the aliases forward_full left of (z, q_mu, q_lv) and the two weights on the
-                # device; ONE backward adds its three gradients to the decoder's and the loss's (ops.FanoutFn: one sum each)
+            if rooted:
+                # LOSS + the features' roots, in the table's order: ONE backward (StepFeature.root)
                 from .. import ops
-                pen = ops.FactorPenaltyFn.apply(*self.model.factor_inputs, self.model.speaker_size, self._fac_coef,
-                                                self.factor_aux)
-                self.model.factor_inputs = None
-                roots.append(pen)
-                seeds.append(ops.unit_seed(vec.device))
-            if smo is not None:
-                # LOSS + penalty: the penalty reads the alias forward_full left of rec_hat, the step's two inputs as its targets
-                # and the two weights on the device; ONE backward adds its gradient to the loss's (ops.FanoutFn: one sum)
-                from .. import ops
-                pen = ops.SmoothingPenaltyFn.apply(*self.model.smooth_inputs, data1, data2, smo["window"], smo["floor"],
-                                                   self._smooth_coef, self.smooth_aux)
-                self.model.smooth_inputs = None
-                roots.append(pen)
-                seeds.append(ops.unit_seed(vec.device))
-            if adv is not None:
-                # q_mu [2 Bh, S + Cn]: the content means are its columns S .. S + Cn - 1; both launches run here, the
-                # classifier's gradients land in its optimiser's buffer, and ONE backward adds the reversed gradient of
-                # q_mu to the loss's own
-                from .. import ops
-                stats = {}
-                ce = adv.loss(outs[2], labels2, self._adv_coef, self.model.speaker_size, stats)
-                self.adv_out, self.adv_pred = stats["out"], stats["row_pred"]
-                roots.append(ce)
-                seeds.append(ops.unit_seed(vec.device))
-            if len(roots) > 1:
-                torch.autograd.backward(roots, seeds)
+                torch.autograd.backward([vec] + [f.root(outs, data1, data2, labels2) for f in rooted],
+                                        [self._loss_seed] + [ops.unit_seed(vec.device)] * len(rooted))
             else:
                 torch.autograd.backward(vec, self._loss_seed)
         else:
@@ -362,8 +279,8 @@ class VariationalBaseModelVAE:
             self.reducer.step(self.optimizer)       # full Adam after an all-reduce, or the sharded step (mode "rs_ag")
         else:
             self.optimizer.step(grad_scale=1.0)
-        if adv is not None:
-            adv.optimizer.step(grad_scale=1.0)
+        for f in rooted:
+            f.after_step()                  # the adversary's own Adam
         return vec.detach() if vec is not None else torch.stack([l.detach() for l in losses])
 
     def _step_graph(self, data1, data2, speaker_ids=None):
@@ -458,8 +375,7 @@ class VariationalBaseModelVAE:
 
     # ---- variational_base_vae.py:58-70
     def step(self, data1, data2, speaker_ids, train=False):
-        if train and (self.kl_sched is not None or self.adversary is not None or self.factor_cfg is not None
-                      or self.smooth_cfg is not None):
+        if train and self._features_on():
             # the same one copy carries the optimiser's step count: the schedules' position is exactly t (a skipped step)
             vec = torch.cat([self.step_async(data1, data2, speaker_ids), self.optimizer.dev_state[0:1]]).tolist()
             self._step_k = int(vec[8])
@@ -501,9 +417,11 @@ class VariationalBaseModelVAE:
         opt = self.optimizer
         clip = getattr(opt, "max_norm", None) is not None
         ema = getattr(opt, "ema_decay", None) is not None
-        sched, adv, fac, smo = self.kl_sched, self.adversary, self.factor_cfg, self.smooth_cfg
-        self.grad_stats = self.ema_stats = self.kl_stats = self.kl_dims = self.adv_stats = self.factor_stats = None
-        self.smooth_stats = None
+        on = self._features_on()
+        self.grad_stats = self.ema_stats = None
+        for f in self.features.values():
+            f.report = f.dims = None
+        self._epoch = max(1, int(epoch))
         # gradient clipping on: the step's norm (optimizer.clip_state[1]) joins running sum / max tensors the same way; a
         # norm that is not finite in float32 (a skipped step, or a huge gradient that was clipped) is counted, not averaged
         if clip:
@@ -511,20 +429,9 @@ class VariationalBaseModelVAE:
             gmax = torch.zeros(1, dtype=torch.float32, device=self.device)
             zero = torch.zeros(1, dtype=torch.float32, device=self.device)
             before = opt.clip_state[5:7].clone()
-        # a KL schedule on (set_kl_schedule): the free counts and the per-dimension KL of every step (kl_aux[2 : 4 + 2 D]) join
-        # a running float64 tensor the same way
-        if sched is not None:
-            self._kl_epoch = max(1, int(epoch))
-            kD = (self.kl_aux.numel() - 4) // 4
-            ksum = f64(2 + 2 * kD)
-        # likewise the four statistics of the speaker adversary (set_speaker_adversary) and the five of the factor penalty
-        # (set_factor_penalty) and of the smoothing penalty (set_smoothing_penalty)
-        if adv is not None:
-            asum = f64(4)
-        if fac is not None:
-            fsum = f64(5)
-        if smo is not None:
-            ssum = f64(5)
+        # every feature of the step that is on: what it records of a step (StepFeature.record) joins a running float64 tensor
+        # the same way, under the feature's name
+        sums = {f.name: f64(f.n_record) for f in on}
         for data1, data2, speaker_ids in train_loader:
             data1 = data1.to(self.device, non_blocking=True).float()
             data2 = data2.to(self.device, non_blocking=True).float()
@@ -532,14 +439,8 @@ class VariationalBaseModelVAE:
             last = self.step_async(data1, data2, speaker_ids)
             steps += 1
             tot.add_(last)
-            if adv is not None:
-                asum.add_(self.adv_out)
-            if fac is not None:
-                fsum.add_(self.factor_aux)
-            if smo is not None:
-                ssum.add_(self.smooth_aux)
-            if sched is not None:
-                ksum.add_(self.kl_aux[2:4 + 2 * kD])
+            for f in on:
+                sums[f.name].add_(f.record())
             if clip:
                 ok = torch.isfinite(opt.clip_state[1:2])
                 norm = torch.where(ok, opt.clip_state[1:2], zero)
@@ -547,50 +448,20 @@ class VariationalBaseModelVAE:
                 torch.maximum(gmax, norm, out=gmax)
         # the epoch's ONE device-to-host copy: every running tensor that is on, by name; while a feature with a schedule is on
         # the optimiser's step count rides along and sets the host's count right
-        parts = {"loss": tot}
-        if sched is not None:
-            parts["kl"] = ksum
-        if adv is not None:
-            parts["adv"] = asum
-        if fac is not None:
-            parts["factor"] = fsum
-        if smo is not None:
-            parts["smooth"] = ssum
+        parts = {"loss": tot, **sums}
         if clip:
             parts.update(gsum=gsum, gmax=gmax, clip_counts=opt.clip_state[5:7] - before)
         if ema:
             parts["ema"] = opt.ema_state[1:3]
-        if sched is not None or adv is not None or fac is not None or smo is not None:
+        if on:
             parts["t"] = opt.dev_state[0:1]
         host = named_to_host(parts)
-        tot, n = host["loss"], max(1, steps)
+        tot = host["loss"]
         if "t" in host:
             self._step_k = int(host["t"][0])
-        if adv is not None:
-            a = host["adv"]
-            self.adv_stats = {"Adv/CE": a[0] / a[1] if a[1] else float("nan"),
-                              "Adv/Accuracy": a[2] / a[1] if a[1] else float("nan"),
-                              "Adv/Weight": self.adv_weight if self.adv_weight is not None else self.adv_weight_at(self._step_k)}
-        if fac is not None:
-            f = host["factor"]
-            w = self.factor_weights if self.factor_weights is not None else self.factor_weights_at(self._step_k)
-            self.factor_stats = {"Factor/TC style": f[0] / n, "Factor/TC content": f[1] / n, "Factor/Shared": f[2] / n,
-                                 "Factor/MI": f[3] / n, "Factor/Penalty": f[4] / n, "Factor/Weight tc": w[0],
-                                 "Factor/Weight shared": w[1]}
-        if smo is not None:
-            f = host["smooth"]
-            w = self.smooth_weights if self.smooth_weights is not None else self.smooth_weights_at(self._step_k)
-            self.smooth_stats = {"Smooth/MS distance dB": f[2] / n, "Smooth/GV ratio dB": f[3] / n, "Smooth/MS loss": f[0] / n,
-                                 "Smooth/GV loss": f[1] / n, "Smooth/Penalty": f[4] / n, "Smooth/Weight ms": w[0],
-                                 "Smooth/Weight gv": w[1]}
-        if sched is not None:
-            k = host["kl"]
-            z1, z2 = [v / n for v in k[2:2 + kD]], [v / n for v in k[2 + kD:2 + 2 * kD]]
-            self.kl_dims = {"epoch": epoch, "steps": steps, "z1": z1, "z2": z2}
-            self.kl_stats = {"KL/Weight": self.kl_weight if self.kl_weight is not None
-                             else self.kl_weight_at(self._step_k, self._kl_epoch),
-                             "KL/Free dims z1": k[0] / n, "KL/Free dims z2": k[1] / n,
-                             "KL/Active dims": sum(1 for v in z1 if v > 0.01)}
+        for f in on:
+            w = f.weights if f.weights is not None else f.weights_at(self._step_k, self._epoch)
+            f.report = f.stats(host[f.name], steps, w, epoch=epoch)
         if clip:
             g = host["gsum"]
             self.grad_stats = {"Grad/Norm mean": g[0] / max(1.0, g[1]), "Grad/Norm max": host["gmax"][0],
@@ -743,20 +614,11 @@ class VariationalBaseModelVAE:
         if os.path.exists(opt):
             sd = torch.load(opt, map_location="cpu")
             self.optimizer.load_state_dict(sd, legacy_layout=os.environ.get("DVAE_OPT_LEGACY_LAYOUT"))
-            # the KL schedule the checkpoint was trained under (load_state_dict has refused a different one): restored when
-            # none was asked for, and continued either way at the step count just loaded (`_step_k` below)
-            saved = sd.get("kl_schedule")
-            if saved is not None and self.kl_sched is None and hasattr(self, "set_kl_schedule"):
-                self.set_kl_schedule(saved["kind"], **{k: saved[k] for k in ("start", "steps", "cycles", "ratio", "free_bits")})
-            # likewise the factor penalty (load_state_dict has refused a different one)
-            saved = sd.get("factor_penalty")
-            if saved is not None and self.factor_cfg is None and hasattr(self, "set_factor_penalty"):
-                self.set_factor_penalty(saved["tc_weight"], saved["shared_weight"], warmup_steps=saved["warmup_steps"])
-            # ... and the smoothing penalty
-            saved = sd.get("smoothing_penalty")
-            if saved is not None and self.smooth_cfg is None and hasattr(self, "set_smoothing_penalty"):
-                self.set_smoothing_penalty(saved["ms_weight"], saved["gv_weight"], window=saved["window"], floor=saved["floor"],
-                                           warmup_steps=saved["warmup_steps"])
+            # the features the checkpoint was trained under (load_state_dict has refused a different configuration): each is
+            # restored when none was asked for, and continued either way at the step count just loaded (`_step_k` below)
+            for f in self.features.values():
+                if not f.on and sd.get(f.key) is not None:
+                    f.restore(sd[f.key])
             if sd.get("cuda_rng_state") is not None and torch.device(self.device).type == "cuda":
                 g = torch.cuda.default_generators[torch.device(self.device).index or 0]
                 if self.reducer is not None and self.reducer.rank > 0:
@@ -924,9 +786,9 @@ class VariationalBaseModelVAE:
             rec = {"epoch": epoch, "Loss/Reconstruction Loss1": r1 / nb, "Loss/Reconstruction Loss2": r2 / nb,
                    "Loss/Reconstruction Loss1 hat": r1h / nb, "Loss/Reconstruction Loss2 hat": r2h / nb,
                    "Loss/Z1 KL Loss": k1 / nb, "Loss/Z2 KL Loss": k2 / nb, "Loss/Z KL Style": ks / nb}
-            # what train() left of the opt-in features that are on: gradient clipping, the weight average (FlatAdam.set_grad_clip,
-            # set_ema), the speaker adversary, the factor penalty, the KL schedule (set_speaker_adversary, ...)
-            for stats in (self.grad_stats, self.ema_stats, self.adv_stats, self.factor_stats, self.smooth_stats, self.kl_stats):
+            # what train() left of what is on: gradient clipping, the weight average (FlatAdam.set_grad_clip, set_ema) and the
+            # features of the step
+            for stats in (self.grad_stats, self.ema_stats, *(f.report for f in self.features.values())):
                 rec.update(stats or {})
             if self.kl_stats and logs_path and self._is_rank0():
                 # beside the logs directory: <log_dir>/kl_dims.json, this epoch's mean KL per latent dimension in nats

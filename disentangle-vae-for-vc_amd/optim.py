@@ -125,14 +125,10 @@ class FlatAdam:
         self.ema, self.ema_state = None, None
         self._dev_ema = None               # (decay, warmup) as last written to ema_state[0], [3]
         self.ema_swapped = False           # True: flat_p holds the average and self.ema the weights (swap_ema)
-        # the KL schedule the trainer runs under (ConvolutionalMulVAE.set_kl_schedule: its parameters as plain numbers, or
-        # None): kept here because its position IS the step count `t`, and so that it rides in state_dict()
-        self.kl_schedule = None
-        # likewise the factor penalty's configuration (ConvolutionalMulVAE.set_factor_penalty), or None: its warm-up's
-        # position is the step count too
-        self.factor_penalty = None
-        # ... and the smoothing penalty's (ConvolutionalMulVAE.set_smoothing_penalty)
-        self.smoothing_penalty = None
+        # the features of the train step the trainer runs under (step_features.py; the setters of ConvolutionalMulVAE), key in
+        # state_dict() -> configuration as plain numbers: kept here because the position of a schedule or a warm-up IS the
+        # step count `t`, and so that they ride in state_dict()
+        self.step_features = {}
         # True: the zero_grad ranges of flat_g are known to be zero (the last Adam launch cleared them after reading and no
         # backward kernel has accumulated since: ops._grad_buf resets it) — zero_grad() is then free
         self._clean = False
@@ -438,33 +434,20 @@ class FlatAdam:
             sd["ema"] = {"decay": self.ema_decay if self.ema_decay is not None else st["decay"], "warmup": self.ema_warmup,
                          "updates": st["updates"],
                          "avg": {n: self._to_ref(n, v).detach().cpu().contiguous() for n, v in self._ema_views()}}
-        if self.kl_schedule is not None:
-            sd["kl_schedule"] = dict(self.kl_schedule)
-        if self.factor_penalty is not None:
-            sd["factor_penalty"] = dict(self.factor_penalty)
-        if self.smoothing_penalty is not None:
-            sd["smoothing_penalty"] = dict(self.smoothing_penalty)
+        sd.update((key, dict(cfg)) for key, cfg in self.step_features.items())
         return sd
 
     def load_state_dict(self, sd, legacy_layout=None):
         """legacy_layout: only for format-1 files (see below): "packed" | "torch"."""
         if sorted(sd["names"]) != sorted(self.names):
             raise ValueError("optimizer state was saved for a different set of parameters")
-        saved_kl = sd.get("kl_schedule")
-        if saved_kl is not None and self.kl_schedule is not None and dict(saved_kl) != dict(self.kl_schedule):
-            raise ValueError(f"optimizer state was trained under the KL schedule {dict(saved_kl)}, this run asks for "
-                             f"{dict(self.kl_schedule)}: resume with the same schedule (or with none: the saved one is "
-                             "restored), or start a new run")
-        saved_fac = sd.get("factor_penalty")
-        if saved_fac is not None and self.factor_penalty is not None and dict(saved_fac) != dict(self.factor_penalty):
-            raise ValueError(f"optimizer state was trained under the factor penalty {dict(saved_fac)}, this run asks for "
-                             f"{dict(self.factor_penalty)}: resume with the same penalty (or with none: the saved one is "
-                             "restored), or start a new run")
-        saved_smo = sd.get("smoothing_penalty")
-        if saved_smo is not None and self.smoothing_penalty is not None and dict(saved_smo) != dict(self.smoothing_penalty):
-            raise ValueError(f"optimizer state was trained under the smoothing penalty {dict(saved_smo)}, this run asks for "
-                             f"{dict(self.smoothing_penalty)}: resume with the same penalty (or with none: the saved one is "
-                             "restored), or start a new run")
+        for key, mine in self.step_features.items():
+            saved = sd.get(key)
+            if saved is not None and dict(saved) != dict(mine):
+                what = key.replace("_", " ").replace("kl ", "KL ")      # "KL schedule", "factor penalty", "smoothing penalty"
+                raise ValueError(f"optimizer state was trained under the {what} {dict(saved)}, this run asks for {dict(mine)}: "
+                                 f"resume with the same {what.split()[-1]} (or with none: the saved one is restored), or start "
+                                 "a new run")
         fmt = int(sd.get("format", 1))
         if fmt == 1:
             # raw flat vectors in the order of ITS `names`.  Two builds wrote this format and nothing in the file tells

@@ -451,18 +451,10 @@ def main(argv=None):
         if all(cfg[k] == get_parse().get_default(k) for k in conv_keys):
             for k in conv_keys:     # likewise the flags of the overlapped conversion
                 del cfg[k]
-        if all(cfg[k] == get_parse().get_default(k) for k in KL_KEYS):
-            for k in KL_KEYS:       # likewise the flags of the KL schedule
-                del cfg[k]
-        if all(cfg[k] == get_parse().get_default(k) for k in ADV_KEYS):
-            for k in ADV_KEYS:      # likewise the flags of the speaker adversary
-                del cfg[k]
-        if all(cfg[k] == get_parse().get_default(k) for k in FACTOR_KEYS):
-            for k in FACTOR_KEYS:   # likewise the flags of the factor penalty
-                del cfg[k]
-        if all(cfg[k] == get_parse().get_default(k) for k in SMOOTH_KEYS):
-            for k in SMOOTH_KEYS:   # ... and of the smoothing penalty
-                del cfg[k]
+        for keys in (KL_KEYS, ADV_KEYS, FACTOR_KEYS, SMOOTH_KEYS):      # likewise the flags of each feature of the train step
+            if all(cfg[k] == get_parse().get_default(k) for k in keys):
+                for k in keys:
+                    del cfg[k]
         with open(os.path.join(args.log_dir, "config.json"), "w") as fp:
             json.dump(cfg, fp, indent=4)
     vsc = ConvolutionalMulVAE(args.dataset, args.samples_length, 80, args.latent_size, args.lr, args.alpha,
