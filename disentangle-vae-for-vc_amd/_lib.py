@@ -189,6 +189,10 @@ SIGNATURES = {
     "dvae_gmm_ws_bytes": (C.c_size_t, [i64, i32, i32]),
     "dvae_gmm_estep": (i32, [vp, i64, i32, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
     "dvae_gmm_score": (i32, [vp, i64, i32, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp]),
+    "dvae_gmm_utt_stats": (i32, [vp, i64, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
+    "dvae_ivec_posterior": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "dvae_ivec_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
+    "dvae_ivec_accumulate": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "dvae_latent_tables": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i64, vp]),
     "dvae_latent_lse": (i32, [vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, vp, i64, vp]),
     "dvae_tsne_nn": (i32, [vp, i64, i64, i32, vp, i64, i64, vp, vp, vp]),
@@ -243,7 +247,11 @@ def lib():
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)  # AttributeError if the .so lacks a declared symbol
+            try:
+                fn = getattr(h, name)
+            except AttributeError:      # symbols are added without a new ABI number: an older build lacks them
+                raise RuntimeError(f"{LIB_PATH} lacks {name} (include/dvae_hip.h): stale library — rebuild the library "
+                                   "with `python -c 'import __graft_entry__ as g; g.build()'`") from None
             fn.restype = res
             fn.argtypes = args
         for name, (res, args) in DEV_SIGNATURES.items():

@@ -30,8 +30,8 @@ if [ "$(cat "$OBJ/.flags" 2>/dev/null || true)" != "$SIG" ] || [ "${FORCE:-0}" =
   echo "$SIG" > "$OBJ/.flags"
 fi
 # vad.hip is part of frontend.hip's translation unit, modspec.hip and msloss.hip of elem.hip's, latents.hip, tsne.hip,
-# adversary.hip and factor.hip of probe.hip's (included at their ends): for staleness they count as headers
-HDR_NEWEST="$(ls -t "$HERE"/*.h "$HERE"/vad.hip "$HERE"/modspec.hip "$HERE"/msloss.hip "$HERE"/latents.hip "$HERE"/tsne.hip "$HERE"/adversary.hip "$HERE"/factor.hip "$HERE"/../../include/*.h | head -1)"
+# adversary.hip, factor.hip and ivector.hip of probe.hip's (included at their ends): for staleness they count as headers
+HDR_NEWEST="$(ls -t "$HERE"/*.h "$HERE"/vad.hip "$HERE"/modspec.hip "$HERE"/msloss.hip "$HERE"/latents.hip "$HERE"/tsne.hip "$HERE"/adversary.hip "$HERE"/factor.hip "$HERE"/ivector.hip "$HERE"/../../include/*.h | head -1)"
 pids=()
 objs=()
 compiled=()

@@ -460,3 +460,4 @@ DVAE_API int dvae_gmm_score(const float* x, int64_t ldx, int col0, int D, const 
 #include "tsne.hip"         // the latent map: the same
 #include "adversary.hip"    // the speaker adversary: the same
 #include "factor.hip"       // the total-correlation / shared-information penalty: the same
+#include "ivector.hip"      // i-vector speaker embeddings: the same

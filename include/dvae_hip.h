@@ -887,6 +887,42 @@ int dvae_gmm_estep(const float* x, int64_t ldx, int col0, int64_t N, int D, cons
 int dvae_gmm_score(const float* x, int64_t ldx, int col0, int D, const int64_t* segs, int nseg, const float* a,
                    const float* mu, const float* prec, int K, int M, double* out, void* stream);
 
+/* ---- i-vector speaker embeddings (python -m dvae_amd.ivector) ----
+ * Replaces nothing of the reference (its speaker encoder is out of scope): the total-variability model of Dehak et al.
+ * (2011) on the UBM above.  Everything is float64 but the UBM's three fp32 tables and the frames.  T [K D][R] (row c D + d)
+ * lives in the whitened space; P [K][R][R], P_c = T_c^T T_c, is computed by the caller in float64 (only j <= i is read).
+ * dvae_gmm_utt_stats: one workgroup per segment {row0, count} of x (as dvae_gmm_score).  gamma is the fp32 posterior of
+ *   dvae_gmm_estep, from the same device functions (the same bits).  n [nseg][K]: n_k = sum_t gamma_tk;
+ *   f [nseg][K D]: g_kd = sum_t gamma_tk x_td, f_kd = (g_kd - n_k (double)mu_kd) sqrt((double)prec_kd) (product, difference,
+ *   product: three roundings; the square root is correctly rounded).  Terms are formed in float64 and every sum is float64
+ *   over t ascending, by one thread: a segment's rows have the same bits whatever else is in the batch.  count <= 0 writes
+ *   +0.0 everywhere.  segs, n and f 8-byte aligned.
+ * dvae_ivec_posterior: one workgroup per utterance u < U, everything on chip (LDS: 2 R (R + 1) + K + 320 doubles):
+ *   L = I + sum_c n_uc P_c (c ascending, one fma per term from +0);  b = T^T f_u, b_r = ((p_0 + p_1) + p_2) + p_3 with p_q
+ *   the sum over rows q, q + 4, ... (ascending, one fma per term from +0);  L = G G^T by columns, the inner products k
+ *   ascending;  every right-hand side (b and, with S, the R columns of I) is solved by ONE thread, G y = r rows ascending,
+ *   G^T x = y rows descending, so w has the same bits with and without S and ll;
+ *   w [U][R] = L^-1 b;  S [U][R][R] = L^-1 + w w^T (optional; S_ij is column j's solve plus w_i w_j by one fma: symmetric
+ *   within the inverse's error, NOT mirrored);  ll [U] = 1/2 sum_i b_i w_i - sum_i ln G_ii (optional; i ascending).
+ *   All orders are a function of (K, D, R) alone.  An utterance with n = 0 and f = 0 gives exactly w = +0.0, S = I,
+ *   ll = +0.0.  L >= I for finite n >= 0, so no pivot is non-positive; a non-finite input gives NaN in that utterance's
+ *   outputs only.
+ * dvae_ivec_accumulate: A [K][R][R] = sum_u n_uc S_u, C [K D][R] = sum_u f_u w_u^T, Ssum [R][R] = sum_u S_u, all OVERWRITTEN.
+ *   The utterances are cut into groups of max(64, ceil(U / 8)) consecutive ones; one thread per output element walks a
+ *   group in order (terms formed in float64: one product, one addition) and writes to the group's slot of ws
+ *   (dvae_ivec_ws_bytes(U, K, D, R) bytes, nothing behind them is touched); a second launch adds the slots in index order.
+ * No atomics: two calls give the same bits.  Null required pointers, U, K, D, R, nseg < 1, K > DVAE_GMM_MAX_K,
+ *   D > DVAE_GMM_MAX_DIM, R > DVAE_IVEC_MAX_R, col0 < 0, ldx < col0 + D or a misaligned float64 / int64 buffer return
+ *   DVAE_EINVAL and launch nothing (dvae_ivec_ws_bytes returns 0). */
+#define DVAE_IVEC_MAX_R 64
+int dvae_gmm_utt_stats(const float* x, int64_t ldx, int col0, int D, const int64_t* segs, int nseg, const float* a,
+                       const float* mu, const float* prec, int K, double* n, double* f, void* stream);
+int dvae_ivec_posterior(const double* n, const double* f, const double* T, const double* P, int U, int K, int D, int R,
+                        double* w, double* S, double* ll, void* stream);
+size_t dvae_ivec_ws_bytes(int U, int K, int D, int R);
+int dvae_ivec_accumulate(const double* n, const double* f, const double* w, const double* S, int U, int K, int D, int R,
+                         void* ws, double* A, double* C, double* Ssum, void* stream);
+
 /* ---- latent report: pairwise posterior log-densities and their log-sum-exps (python -m dvae_amd.latents) ----
  * Replaces nothing of the reference (its only latent diagnostic is compute_KL_delta_VAE, model/disentangled_vae.py:333-345,
  * unused): the minibatch-weighted-sampling decomposition of Chen et al. (2018) taken over a whole corpus of N posteriors
